@@ -12,6 +12,11 @@ already resident in HBM when the timed region starts (BASELINE config[1]).
 N > 1: one process per GPU, independent pairs per rank (no data-path
 collective; RCCL only for the barrier and the max-over-ranks time), weak scaling.
 Prints ONE JSON line on rank 0.
+
+A plain run measures the headline loop only.  --full adds the roofline pass, the
+other workloads of BASELINE.json and the CPU baselines to the line.
+--dump-outputs DIR writes the last timed step's results as .npy files (the inputs
+are seeded: the same arguments give the same inputs run to run).
 """
 from __future__ import annotations
 
@@ -60,11 +65,18 @@ def parse():
                          "host work is mostly inside library calls, which release the GIL, so three threads enqueue three "
                          "streams side by side: +6 %% over the single scheduler), or ONE host thread resuming each step "
                          "when its device->host fetch has landed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also measure what the headline figure does not need: the roofline pass, "
+                         "the extra workloads and the CPU baselines (each can still be left out with its --no-* switch).  "
+                         "Off by default: a plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller (the poses and the "
+                         "per-pair RANSAC / voxel counts of its pairs) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the extra workloads block (Predator config 3, FatBN-128, config 5), measured after the "
-                         "headline loop")
+                    help="with --full: skip the extra workloads block (Predator config 3, FatBN-128, config 5), measured "
+                         "after the headline loop")
     ap.add_argument("--pairs-per-step", type=int, default=1,
                     help="independent pairs batched into one encoder call per step (value counts pairs, not steps)")
     ap.add_argument("--pairs-total", type=int, default=0,
@@ -637,12 +649,12 @@ def main():
             res = pipe.register_batch([pairs[j] for j in idx], seeds=[seeds4[j] for j in idx])
             for j, (T_, _) in zip(idx, res):
                 poses4[j] = T_
-            return res[-1]
+            return res
         if B == 1:
             a, b = pairs[i % len(pairs)]
-            return pipe(a, b, seed=i)
+            return [pipe(a, b, seed=i)]
         batch = [pairs[(i * B + j) % len(pairs)] for j in range(B)]
-        return pipe.register_batch(batch, seeds=[i * B + j for j in range(B)])[-1]
+        return pipe.register_batch(batch, seeds=[i * B + j for j in range(B)])     # [(T, info)] of the step's pairs
 
     # S independent steps in flight: worker w owns HIP stream w and runs steps w, w+S, w+2S, ...  The worker threads
     # are PERSISTENT (created once, here in the setup): no thread, stream, HSA queue or allocator pool is first touched
@@ -713,7 +725,7 @@ def main():
             res, done_at = run_pipelined(make_step, range(first, last), streams)
             host_busy["s"], host_busy["steps"] = run_pipelined.last_host_busy_s, last - first
             for i, r in res.items():
-                results[i] = r[-1]
+                results[i] = r
             step_log.extend((i, 0, t, t) for i, t in done_at)
             for st in hip_streams:
                 st.synchronize()
@@ -761,7 +773,8 @@ def main():
     samp0 = ops.ransac_sampling_launches()
     t0 = time.perf_counter()
     run_steps(first, first + args.steps)     # EXACTLY `steps` steps, `streams` in flight
-    T, info = results[first + args.steps - 1]
+    last_step = results[first + args.steps - 1]
+    T, info = last_step[-1]
     torch.cuda.synchronize()
     barrier()
     elapsed_local = time.perf_counter() - t0
@@ -840,7 +853,17 @@ def main():
                    "per_rank_pairs_per_s": [float(r[0] / r[1]) for r in stats.tolist()]},
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last timed step received: B poses + the per-pair info fields, in step order
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumps = {"poses": np.stack([np.asarray(T_, dtype=np.float64) for T_, _ in last_step])}
+        for key in sorted(last_step[0][1]):
+            dumps[key] = np.array([info_[key] for _, info_ in last_step], dtype=np.float64)
+        for name, arr in dumps.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
+        log(f"dumped {sorted(dumps)} of step {args.steps - 1} of the timed loop to {args.dump_outputs}")
+
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented pass: HIP events around every sparse-conv launch, on the launch stream
         prof = ops.SpconvProfile()
         ops.PROFILE = prof
@@ -917,11 +940,11 @@ def main():
             "by_batch": by_batch,
             "by_kernel": {names[k]: v for k, v in sorted(legs.items())},
         }
-    if rank == 0 and world == 1 and not args.no_workloads:
+    if rank == 0 and world == 1 and args.full and not args.no_workloads:
         if args.match_lanes > 1:
             ops.set_match_lanes(1)      # the side workloads keep several steps in flight themselves
         out["workloads"] = extra_workloads(dev, log, cpu_baselines=not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline (oracle on host cores) ...")
         out["cpu_baseline"] = cpu_baseline(model.state_dict(), args.model, args.n_out, host_pairs,
                                            args.ransac_iters)

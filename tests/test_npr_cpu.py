@@ -1,26 +1,28 @@
 """CPU: the NPR MLP mirror has the reference's module / parameter layout (FCGF_APR/model/mlp.py)."""
-import importlib.util
+import hashlib
+import json
 import os
 
-import pytest
 import torch
 
 from apr_amd.fcgf.lib import apg
 
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/FCGF_APR/model/mlp.py"), reason="reference not present")
+
 def test_generative_mlp_state_dict_equals_reference():
-    spec = importlib.util.spec_from_file_location("ref_mlp", "/root/reference/FCGF_APR/model/mlp.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """Same keys in the same order, shapes, dtypes and bits of every tensor as the reference's modules built after the same
+    seed (tests/golden/fcgf_mlp_ref.json, written by make_reference_modules_golden.py from the reference's mlp.py)."""
+    with open(os.path.join(GOLD, "fcgf_mlp_ref.json")) as f:
+        ref = json.load(f)
     for name in ("GenerativeMLP", "GenerativeMLP_98", "GenerativeMLP_54"):
         torch.manual_seed(0)
-        a = getattr(ref, name)(in_channel=32, out_points=4)
-        torch.manual_seed(0)
-        b = getattr(apg, name)(in_channel=32, out_points=4)
-        sa, sb = a.state_dict(), b.state_dict()
-        assert list(sa.keys()) == list(sb.keys())
-        assert all(torch.equal(sa[k], sb[k]) for k in sa)
+        sb = getattr(apg, name)(in_channel=32, out_points=4).state_dict()
+        assert [k for k, *_ in ref[name]] == list(sb.keys()), name
+        for k, shape, dtype, sha in ref[name]:
+            v = sb[k]
+            assert list(v.shape) == shape and str(v.dtype) == dtype, (name, k)
+            assert hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest() == sha, (name, k)
 
 
 def test_layout_without_reference():

@@ -1,7 +1,6 @@
-"""CPU: the KPFCNN restatement against the reference's own outputs (golden) and, when /root/reference is
-present (build container), against the imported reference modules on a tiny batch."""
+"""CPU: the KPFCNN restatement against the reference's own outputs (golden), and its single ops against outputs of the
+imported reference modules on small random inputs (tests/golden/predator_blocks_ref.npz)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -52,49 +51,17 @@ def test_oracle_reproduces_reference_golden():
     assert np.abs(ov.numpy() - g["overlap"]).max() < 1e-4 and np.abs(sal.numpy() - g["saliency"]).max() < 1e-4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Predator_APR") or not PREF.available(),
-                    reason="reference not present (GPU box)")
-def test_oracle_blocks_against_imported_reference(tmp_path):
-    """Import the reference's blocks.py / gcn.py and compare single ops on random inputs."""
-    ref_root = "/root/reference/Predator_APR"
-    os.makedirs(tmp_path / "kernels" / "dispositions")
-    import shutil
-    shutil.copy(os.path.join(ref_root, "kernels/dispositions/k_015_center_3D.ply"), tmp_path / "kernels" / "dispositions")
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    sys.path.insert(0, ref_root)
-    try:
-        from models import blocks as RB
-        from models import gcn as RG
-        rng = np.random.default_rng(0)
-        np.random.seed(1)
-        torch.manual_seed(1)
-        conv = RB.KPConv(15, 3, 16, 24, 1.2, 2.55)
-        s = torch.from_numpy(rng.uniform(-4, 4, (300, 3)).astype(np.float32))
-        inds = torch.from_numpy(rng.integers(0, 301, (200, 19)).astype(np.int64))
-        x = torch.from_numpy(rng.standard_normal((300, 16)).astype(np.float32))
-        with torch.no_grad():
-            ref = conv(s[:200], s, inds, x)
-        got = KO.kpconv(s[:200], s, inds, x, conv.weights.detach(), conv.kernel_points.detach(), 1.2)
-        assert torch.allclose(ref, got, atol=1e-5)
-        sa = RG.SelfAttention(32, k=10).eval()
-        coords = torch.from_numpy(rng.uniform(-10, 10, (150, 3)).astype(np.float32))
-        feats = torch.from_numpy(rng.standard_normal((150, 32)).astype(np.float32))
-        with torch.no_grad():
-            ref = sa(coords.t().unsqueeze(0), feats.t().unsqueeze(0))[0].t()
-        sd = {"p." + k: v for k, v in sa.state_dict().items()}
-        got = KO.self_attention(sd, "p.", coords, feats, 10)
-        assert torch.allclose(ref, got, atol=1e-4)
-        ap = RG.AttentionalPropagation(64, 4).eval()
-        a = torch.from_numpy(rng.standard_normal((70, 64)).astype(np.float32))
-        b = torch.from_numpy(rng.standard_normal((90, 64)).astype(np.float32))
-        with torch.no_grad():
-            ref = ap(a.t().unsqueeze(0), b.t().unsqueeze(0))[0].t()
-        sd = {"p." + k: v for k, v in ap.state_dict().items()}
-        got = KO.attentional_propagation(sd, "p.", a, b, 4)
-        assert torch.allclose(ref, got, atol=1e-4)
-    finally:
-        os.chdir(cwd)
-        sys.path.remove(ref_root)
-        for k in [k for k in sys.modules if k.split('.')[0] in ('models', 'kernels', 'lib', 'configs')]:
-            del sys.modules[k]
+def test_oracle_blocks_against_imported_reference():
+    """The oracle's KPConv / SelfAttention / AttentionalPropagation against the reference's blocks.py / gcn.py modules run
+    on seeded random inputs (inputs, parameters and outputs stored by tests/golden/make_reference_modules_golden.py)."""
+    g = np.load(os.path.join(GOLD, "predator_blocks_ref.npz"))
+    t = {k: torch.from_numpy(g[k]) for k in g.files}
+    s = t["kp_s"]
+    got = KO.kpconv(s[:200], s, t["kp_inds"], t["kp_x"], t["kp_weights"], t["kp_kernel_points"], 1.2)
+    assert torch.allclose(t["kp_out"], got, atol=1e-5)
+    sd = {"p." + k[len("sa_sd."):]: v for k, v in t.items() if k.startswith("sa_sd.")}
+    got = KO.self_attention(sd, "p.", t["sa_coords"], t["sa_feats"], 10)
+    assert torch.allclose(t["sa_out"], got, atol=1e-4)
+    sd = {"p." + k[len("ap_sd."):]: v for k, v in t.items() if k.startswith("ap_sd.")}
+    got = KO.attentional_propagation(sd, "p.", t["ap_a"], t["ap_b"], 4)
+    assert torch.allclose(t["ap_out"], got, atol=1e-4)
