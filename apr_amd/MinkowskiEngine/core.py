@@ -486,18 +486,19 @@ class _ConvBase(nn.Module):
         swapped); `plist`: the reverse map's pair lists."""
         want_bf3 = plist is not None or nbr_bwd is None
         w_bf3 = self.packed_weight_T(flip, tile=False, bf3=True)[1] if want_bf3 else None
-        wp = None if self._bf3_only(plist, self.out_channels, w_bf3) else self.packed_weight_T(flip, tile=True, bf3=False)[0]
+        # the tile pack is built by ops.spconv only when the launch reads it (a K = 1 map on the dense kernels does not)
+        wp = None if self._bf3_only(plist, self.out_channels, w_bf3) else \
+            (lambda: self.packed_weight_T(flip, tile=True, bf3=False)[0])
         os_pairs = plist if isinstance(plist, ops.OsPairs) else None
         return ops.spconv(dout, nbr_bwd, self.kernel_volume if nbr_bwd is not None else 1, self.out_channels,
                           self.in_channels, wp, n_out=n_in, plist=None if os_pairs is not None else plist,
                           w_bf3=w_bf3, os_pairs=os_pairs)
 
     def run(self, feats, nbr, n_out, scale=None, shift=None, residual=None, relu=False, out=None, batch=None,
-            plist=None, l2norm=False, raw=False):
+            plist=None, l2norm=False):
         """Raw fused launch on feature rows (used by the fused encoder plan); `batch` defers the launch; `l2norm`
-        (batched launches only): rows of the result divided by their 2-norm in the same launch; `raw`: no bias either (the
-        training path's norm follows)."""
-        if shift is None and self.bias is not None and not raw:
+        (batched launches only): rows of the result divided by their 2-norm in the same launch."""
+        if shift is None and self.bias is not None:
             shift = self.bias.detach().view(-1)
         fn = ops.spconv if batch is None else batch.add
         os_pairs = plist if isinstance(plist, ops.OsPairs) else None     # output-stationary tile lists
@@ -506,8 +507,12 @@ class _ConvBase(nn.Module):
             raise AprHipError("conv.run(l2norm=True) needs a SpconvBatch")
         w_bf3 = self.packed_weight_bf3() if (plist is not None or nbr is None) else None
         # a direct (un-batched) launch on a route that reads the split image alone does not need the tile pack: a training
-        # step re-packs every kernel once per optimizer step, so what is not read is not built
-        wp = None if (batch is None and self._bf3_only(plist, self.in_channels, w_bf3)) else self.packed_weight()
+        # step re-packs every kernel once per optimizer step, so what is not read is not built (ops.spconv builds it on
+        # demand: the dense K = 1 kernels do not read it either)
+        if batch is None:
+            wp = None if self._bf3_only(plist, self.in_channels, w_bf3) else self.packed_weight
+        else:
+            wp = self.packed_weight()
         return fn(feats, nbr, self.kernel_volume if nbr is not None else 1, self.in_channels,
                   self.out_channels, wp, scale=scale, shift=shift, residual=residual,
                   relu=relu, out=out, n_out=n_out, plist=None if os_pairs is not None else plist,

@@ -75,6 +75,9 @@ __global__ __launch_bounds__(256) void k_wgrad_partial(const float* __restrict__
 //   until the end: S_k partials per offset instead of one per 512 rows); the rows of step t + 1 are in flight (registers)
 //   under the MFMAs of step t, one barrier per step.  k_wgrad_reduce_work sums the S_k partials of an offset in ascending
 //   order: no atomics, the same bits every run.
+//   The work-item decode below is written in select form on purpose: as `if (centre) {...} else {...}` hipcc 7.2 -O3 kept
+//   S = S_c on both paths, and every non-centre offset lost its row blocks past the first.  Regression guard:
+//   tests/test_backward_gpu.py::test_wgrad_every_offset_sees_every_row_block (each offset of dW on its own against fp64).
 // ---------------------------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));

@@ -407,7 +407,8 @@ class ResUNet2(ME.MinkowskiNetwork):
                     if conv.out_channels % 64 == 0 else None
                 pl_b = None
                 if feats.requires_grad and ok3 and conv.in_channels % 64 == 0:
-                    pl_b = lists(stage_name, conv, mb, conv.out_channels, conv.packed_weight_T(flip)[1] is not None)
+                    pl_b = lists(stage_name, conv, mb, conv.out_channels,
+                                 conv.packed_weight_T(flip, tile=False, bf3=True)[1] is not None)
             cfg = dict(conv=conv, bn=norm, nbr=nbr, plist=pl, nbr_bwd=nbr_b, plist_bwd=pl_b, flip=flip, relu=relu, n_out=n_out,
                        segs=segs.get(m[1] if m is not None else 1))
             bn = norm.bn if norm is not None else None

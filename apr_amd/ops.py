@@ -667,7 +667,8 @@ def spconv(x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu
 
     x / residual / out may be column slices of wider row-major buffers.  With `plist` (the PairList of `nbr`)
     the launch takes the weight-stationary path (apr_spconv_ws_fwd); with `os_pairs` (the OsPairs of `nbr`) and the
-    split weights the output-stationary one (apr_spconv_os_fwd).
+    split weights the output-stationary one (apr_spconv_os_fwd).  `wp` may be a callable that returns the tile pack: it is
+    called only when the chosen kernel reads that pack.
     """
     if os_pairs is not None and w_bf3 is not None and nbr is not None:
         return spconv_os(x, os_pairs, cin, cout, w_bf3, scale=scale, shift=shift, residual=residual, relu=relu, out=out)
@@ -705,6 +706,8 @@ def spconv(x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu
             check(lib.apr_dense_gemm_bf3(ptr(x), ldi, n_out, cin, cout, ptr(w_bf3), ptr(scale), ptr(shift), ptr(residual), ldr,
                                          int(bool(relu)), ptr(out), ldo, stream()))
             return out
+    if callable(wp):
+        wp = wp()
     use_ws = plist is not None and nbr is not None and ws_supported(K, cin, cout)
     use_ws3 = use_ws and isinstance(plist, PairList3)
     if use_ws3 and (w_bf3 is None or not ws3_supported(K, cin, cout)):
@@ -907,7 +910,8 @@ class ConvBnActFunction(torch.autograd.Function):
       backward  apr_bn_train_bwd (ReLU mask, dgamma, dbeta, dz, the residual's gradient), the input gradient = the SAME
                 routed convolution over the reverse map with the flipped-transposed kernel (packed once per optimizer step),
                 the kernel gradient = apr_spconv_wgrad on the bf16-split MFMA.
-    Without a norm (`bn` None: the two K = 1 layers behind the decoder) the bias add / ReLU ride in the conv epilogue.
+    Without a norm (`bn` None: the two K = 1 layers behind the decoder) the bias add / ReLU ride in the conv epilogue; with one,
+    a conv bias still rides in the epilogue (the batch statistics and running_mean see it) and gets col_sums(dz) back.
     `cfg`: a dict (conv, bn, nbr, plist, nbr_bwd, plist_bwd, flip, relu, n_out[, segs: the row offsets of the stacked forward
     calls, each with its own batch statistics])."""
 
@@ -917,7 +921,7 @@ class ConvBnActFunction(torch.autograd.Function):
         x = x.contiguous()
         n_out = cfg["n_out"]
         if bn is not None:
-            z = conv.run(x, cfg["nbr"], n_out, plist=cfg["plist"], raw=True)
+            z = conv.run(x, cfg["nbr"], n_out, plist=cfg["plist"])
             y, mean, rstd = bn_train_fwd(z, bn.bn, residual=residual, relu=cfg["relu"], segments=cfg.get("segs"))
             ctx.save_for_backward(x, kernel, z, y, mean, rstd, gamma)
         else:
@@ -948,8 +952,8 @@ class ConvBnActFunction(torch.autograd.Function):
                 check(_lib_().apr_act_backward(ptr(dy), c, ptr(y), c, dy.shape[0], c, 1, 0.0, ptr(dz), c, stream()))
             if ctx.has_res and ctx.needs_input_grad[5]:
                 dres = dz
-            if conv.bias is not None and ctx.needs_input_grad[4]:
-                dbias = col_sums(dz).reshape(conv.bias.shape)
+        if conv.bias is not None and ctx.needs_input_grad[4]:
+            dbias = col_sums(dz).reshape(conv.bias.shape)
         K, cin, cout = conv.kernel_volume if cfg["nbr"] is not None else 1, conv.in_channels, conv.out_channels
         din = dw = None
         if ctx.needs_input_grad[0]:

@@ -303,3 +303,38 @@ def test_input_gradient_kernel_image_packs_straight_from_the_parameter(K, cin, c
     two_step = ops.pack_weights_bf3(ops.weights_flip_transpose(w, flip))
     assert direct is not None and two_step is not None
     assert torch.equal(direct, two_step)
+
+
+@pytest.mark.parametrize("n,cin,cout", [(6667, 128, 128), (6667, 64, 128), (20000, 64, 64), (14000, 128, 128)])
+@pytest.mark.parametrize("same_level", [False, True])
+def test_wgrad_every_offset_sees_every_row_block(dev, n, cin, cout, same_level):
+    """Regression guard of k_wgrad_bf3's work-item decode (hipcc 7.2 -O3 once kept the centre offset's split
+    count on every path, and each non-centre offset lost its row blocks past the first).  Maps of 13 .. 40 512-row blocks
+    with a full centre column, each offset of dW on its own within 2e-6 of fp64 -- a whole-tensor norm hides one offset."""
+    rng = np.random.default_rng(n + cin + cout)
+    K = 27
+    nbr = rng.integers(0, n, size=(n, K)).astype(np.int32)
+    nbr[rng.random((n, K)) > 0.25] = -1
+    nbr[:, 13] = np.arange(n)
+    x = torch.from_numpy(rng.standard_normal((n, cin)).astype(np.float32)).to(dev)
+    g = torch.from_numpy(rng.standard_normal((n, cout)).astype(np.float32)).to(dev)
+    nb = torch.from_numpy(nbr).to(dev)
+    dw = ops.spconv_wgrad(x, g, nb, K, cin, cout, same_level=same_level)
+    errs = []
+    for k in range(K):
+        j = torch.nonzero(nb[:, k] >= 0).squeeze(1)
+        ref = x[nb[j, k].long()].double().t() @ g[j].double()
+        errs.append(rel_l2(dw[k].cpu(), ref.cpu()))
+    assert max(errs) < 2e-6, [(k, e) for k, e in enumerate(errs) if e >= 2e-6]
+
+
+@pytest.mark.parametrize("K", [1, 8, 27])
+@pytest.mark.parametrize("flip", [False, True])
+def test_weights_flip_transpose_is_exact(dev, K, flip):
+    """apr_weights_flip_transpose is a permutation: bit for bit W.flip(0).transpose(1, 2) (mirrored offsets) or
+    W.transpose(1, 2), at widths that are not multiples of a tile."""
+    g = torch.Generator(device="cpu").manual_seed(K + 100 * flip)
+    w = torch.randn(K, 96, 40, generator=g).to(dev)
+    want = (w.flip(0) if flip else w).transpose(1, 2)
+    got = ops.weights_flip_transpose(w, flip)
+    assert got.shape == want.shape and torch.equal(got, want)
