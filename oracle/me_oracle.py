@@ -32,8 +32,13 @@ Conventions (shared with the HIP kernels):
   * `sparse_quantize` keeps the first input row of every voxel, in ascending
     row order.
 
-Everything is numpy / torch-CPU float32, vectorised so a 20 k-point frame
-encodes in seconds.
+Everything is numpy / torch-CPU, vectorised so a 20 k-point frame encodes in
+seconds.  Features follow their dtype: numpy input becomes float32 (as the HIP
+path), a float32 / float64 torch tensor keeps its dtype, so `model.double()`
+runs the whole network in float64.
+
+`relu(x, pin)` can take a pinned decision: (coords [n,4], mask [n,c]) recorded
+elsewhere (the HIP node's `y > 0`), matched to x's rows by coordinates.
 """
 from __future__ import annotations
 
@@ -157,7 +162,8 @@ class CoordinateManager:
 
 class SparseTensor:
     def __init__(self, features, coordinates=None, coordinate_map_key=None, coordinate_manager=None):
-        self.F = torch.as_tensor(features, dtype=torch.float32)
+        keep = torch.is_tensor(features) and features.dtype in (torch.float32, torch.float64)
+        self.F = features if keep else torch.as_tensor(features, dtype=torch.float32)
         if coordinates is not None:
             self.coordinate_manager = CoordinateManager(np.asarray(coordinates))
             self.coordinate_map_key = 1
@@ -190,7 +196,7 @@ def conv_forward(x: SparseTensor, W: torch.Tensor, kernel_size, stride, bias=Non
         fwd = cm.get_map(ts_out, ts, kernel_size)  # fine -> coarse
         nbr = transpose_map(fwd, len(cm.get_coords(ts_out)))
     n_out = nbr.shape[0]
-    out = torch.zeros(n_out, W.shape[2], dtype=torch.float32)
+    out = torch.zeros(n_out, W.shape[2], dtype=x.F.dtype)
     for o in range(nbr.shape[1]):
         j = np.nonzero(nbr[:, o] >= 0)[0]
         if len(j) == 0:
@@ -206,8 +212,30 @@ def batch_norm(x: SparseTensor, bn: torch.nn.BatchNorm1d):
     return x._like(bn(x.F))
 
 
-def relu(x: SparseTensor):
-    return x._like(torch.relu(x.F))
+def align_rows(coords_src, coords_dst):
+    """perm with coords_src[perm] == coords_dst row for row (the same coordinate set in another row order)."""
+    ks, kd = pack_keys(np.asarray(coords_src)), pack_keys(np.asarray(coords_dst))
+    order = np.argsort(ks, kind="stable")
+    pos = np.minimum(np.searchsorted(ks[order], kd), len(ks) - 1)
+    perm = order[pos]
+    if len(ks) != len(kd) or not np.array_equal(ks[perm], kd):
+        raise ValueError("align_rows: the two maps hold different coordinates")
+    return perm
+
+
+def relu(x: SparseTensor, pin=None):
+    """ReLU; `pin` = (coords [n,4], mask [n,c] bool): the mask decides instead of the sign, rows matched by coordinates.
+    A pinned ReLU is x * mask, so applying the same pin twice is applying it once."""
+    if pin is None:
+        return x._like(torch.relu(x.F))
+    coords, mask = pin
+    mask = torch.as_tensor(mask)
+    C = x.coordinate_manager.get_coords(x.coordinate_map_key)
+    coords = np.asarray(coords)
+    if not (coords.shape == C.shape and np.array_equal(coords, C)):
+        mask = mask[torch.from_numpy(align_rows(coords, C).astype(np.int64))]
+    assert mask.shape == x.F.shape, (tuple(mask.shape), tuple(x.F.shape))
+    return x._like(x.F * mask.to(x.F.dtype))
 
 
 def cat(a: SparseTensor, b: SparseTensor):

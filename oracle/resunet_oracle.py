@@ -9,6 +9,11 @@ Structure follows `/root/reference/FCGF_APR/model/resunet.py:10-193`
 so one state_dict drives both this oracle and the HIP model.
 
 PARITY UNPINNED against upstream MinkowskiEngine (see me_oracle.py header).
+
+`forward(x, pins)`: optional pinned ReLU decisions, {module name of the unit that owns the ReLU: (coords, mask)} with the
+names of the HIP model's fused training nodes -- `blockN.conv1` (the ReLU after blockN.norm1), `blockN.conv2` (after the
+residual), `conv1_tr`.  The ReLU the network applies to a block's output a second time takes the block's own pin (the
+identity on the block's output, as in the fused path).  Without pins nothing changes.
 """
 from __future__ import annotations
 
@@ -18,6 +23,11 @@ import torch
 import torch.nn as nn
 
 from . import me_oracle as ME
+
+
+# the ReLU sites of ResUNet2.forward in call order, each under the name of the fused training node that owns its pin
+RELU_SITES = [n for b in ("1", "2", "3", "4", "4_tr", "3_tr", "2_tr")
+              for n in (f"block{b}.conv1", f"block{b}.conv2", f"block{b}.conv2")] + ["conv1_tr"]
 
 
 class OConv(nn.Module):
@@ -83,11 +93,12 @@ class OBasicBlock(nn.Module):
         self.conv2 = OConv(c, c, 3)
         self.norm2 = get_norm(norm_type, c, bn_momentum)
 
-    def forward(self, x):
-        out = ME.relu(self.norm1(self.conv1(x)))
+    def forward(self, x, pins=None, name=None):
+        pin = (lambda k: pins.get(f"{name}.{k}")) if pins else (lambda k: None)
+        out = ME.relu(self.norm1(self.conv1(x)), pin("conv1"))
         out = self.norm2(self.conv2(out))
         out = out._like(out.F + x.F)
-        return ME.relu(out)
+        return ME.relu(out, pin("conv2"))
 
 
 class ResUNet2(nn.Module):
@@ -125,23 +136,25 @@ class ResUNet2(nn.Module):
         self.conv1_tr = OConv(C[1] + T[2], T[1], 1)
         self.final = OConv(T[1], out_channels, 1, bias=True)
 
-    def forward(self, x):
-        out_s1 = self.block1(self.norm1(self.conv1(x)))
-        out = ME.relu(out_s1)
-        out_s2 = self.block2(self.norm2(self.conv2(out)))
-        out = ME.relu(out_s2)
-        out_s4 = self.block3(self.norm3(self.conv3(out)))
-        out = ME.relu(out_s4)
-        out_s8 = self.block4(self.norm4(self.conv4(out)))
-        out = ME.relu(out_s8)
+    def forward(self, x, pins=None):
+        pins = pins or {}
+        p = lambda name: pins.get(name)
+        out_s1 = self.block1(self.norm1(self.conv1(x)), pins, "block1")
+        out = ME.relu(out_s1, p("block1.conv2"))
+        out_s2 = self.block2(self.norm2(self.conv2(out)), pins, "block2")
+        out = ME.relu(out_s2, p("block2.conv2"))
+        out_s4 = self.block3(self.norm3(self.conv3(out)), pins, "block3")
+        out = ME.relu(out_s4, p("block3.conv2"))
+        out_s8 = self.block4(self.norm4(self.conv4(out)), pins, "block4")
+        out = ME.relu(out_s8, p("block4.conv2"))
 
-        out = self.block4_tr(self.norm4_tr(self.conv4_tr(out)))
-        out = ME.cat(ME.relu(out), out_s4)
-        out = self.block3_tr(self.norm3_tr(self.conv3_tr(out)))
-        out = ME.cat(ME.relu(out), out_s2)
-        out = self.block2_tr(self.norm2_tr(self.conv2_tr(out)))
-        out = ME.cat(ME.relu(out), out_s1)
-        out = ME.relu(self.conv1_tr(out))
+        out = self.block4_tr(self.norm4_tr(self.conv4_tr(out)), pins, "block4_tr")
+        out = ME.cat(ME.relu(out, p("block4_tr.conv2")), out_s4)
+        out = self.block3_tr(self.norm3_tr(self.conv3_tr(out)), pins, "block3_tr")
+        out = ME.cat(ME.relu(out, p("block3_tr.conv2")), out_s2)
+        out = self.block2_tr(self.norm2_tr(self.conv2_tr(out)), pins, "block2_tr")
+        out = ME.cat(ME.relu(out, p("block2_tr.conv2")), out_s1)
+        out = ME.relu(self.conv1_tr(out), p("conv1_tr"))
         out = self.final(out)
         if self.normalize_feature:
             return out._like(out.F / torch.norm(out.F, p=2, dim=1, keepdim=True))

@@ -9,9 +9,36 @@ from apr_amd import ops, synth
 from apr_amd.fcgf.lib.trainer import HardestContrastiveLoss
 from oracle import match_pose_oracle as MO
 from oracle import me_oracle as OME
-from tests.helpers import model_pair, rel_l2
+from tests.helpers import EncoderRecorder, ReluSpy, model_pair, oracle_copy, rel_l2, stat_err
 
 pytestmark = pytest.mark.gpu
+
+# the float64 legs of the two whole-encoder gradient tests: HIP ReLU masks pinned in the oracle (tests/helpers.py).
+# Measured on an MI355X (worst of the tile / default / FatBN-fused legs): y 6.2e-7, every parameter gradient 2.1e-6,
+# running statistics 1.7e-6, 1 pinned entry in 2.4 M / 5.2 M where the fp64 sign differs, at 1.0e-7 of its layer's RMS.
+TIGHT = {"y": 3e-6, "grad": 1e-5, "running": 1e-5, "flip_z/rms": 1e-6}
+
+
+def _fp64_leg(monkeypatch, rec, name, out_ch, state0, C, F, hy, grads, buffers, proj, calls=None, tag=""):
+    """The float64 oracle from state0 with the HIP run's ReLU masks pinned: features, every parameter gradient and the
+    running statistics at the TIGHT bars; every pinned mask is legitimate (a float64 disagreement is fp32 noise of 0)."""
+    om = oracle_copy(name, state0, out_ch)
+    spy = ReluSpy(monkeypatch)
+    y = om(OME.SparseTensor(torch.as_tensor(F).double(), coordinates=C), rec.pins([C], calls)[0]).F
+    (y * torch.as_tensor(proj).cpu().double()).sum().backward()
+    flips, flip_z, watched = spy.summary()
+    og, ob = dict(om.named_parameters()), dict(om.named_buffers())
+    worst = {"y": rel_l2(hy.detach().cpu(), y.detach()),
+             "grad": max(rel_l2(g.cpu(), og[n].grad) for n, g in grads.items()),
+             "running": max(stat_err(b, ob[n]) for n, b in buffers.items() if "running" in n),
+             "flip_z/rms": flip_z}
+    print(f"[fp64 leg {tag}] flips {flips}/{watched}, " + ", ".join(f"{q} {v:.2e}" for q, v in worst.items()))
+    assert flips <= max(4, 1e-5 * watched), (flips, watched)
+    for q, v in worst.items():
+        assert v <= TIGHT[q], (q, v, TIGHT[q])
+    for n, b in buffers.items():
+        if n.endswith("num_batches_tracked"):
+            assert int(b) == int(ob[n]), n
 
 
 def _ref_conv(x, nbr, W):
@@ -132,6 +159,8 @@ def test_encoder_training_step_gradients(dev, routing, monkeypatch):
         monkeypatch.setenv("APR_WS_STAGES", "none")
     om, hm = model_pair("ResUNetBN2C", 32)
     om.train(); hm.train()
+    state0 = {k: v.clone() for k, v in om.state_dict().items()}
+    rec = EncoderRecorder(monkeypatch, hm)
     xyz, _, _ = synth.make_pair(5, n_beams=16, n_azimuth=700)
     c, _ = OME.sparse_quantize(xyz / np.float32(0.3), return_index=True)
     C = OME.batched_coordinates([c])
@@ -154,6 +183,10 @@ def test_encoder_training_step_gradients(dev, routing, monkeypatch):
             assert torch.allclose(b.cpu(), ob[name], rtol=1e-3, atol=1e-5), name
         if name.endswith("num_batches_tracked"):
             assert int(b) == int(ob[name]) == 1, name
+    # the same gradients at a tight bar: float64 oracle with the HIP ReLU masks pinned (no kink can flip between the two)
+    assert len(rec.nodes) == 23
+    _fp64_leg(monkeypatch, rec, "ResUNetBN2C", 32, state0, C, F, hy, {n: p.grad for n, p in hm.named_parameters()},
+              dict(hm.named_buffers()), proj, tag=routing)
 
 
 def test_hardest_contrastive_loss_backward(dev):
@@ -228,6 +261,7 @@ def test_fused_training_path_matches_module_path_and_is_reproducible(dev, monkey
     _, hm = model_pair("ResUNetFatBN", 128, seed=2)
     hm.train()
     state0 = {k: v.clone() for k, v in hm.state_dict().items()}
+    rec = EncoderRecorder(monkeypatch, hm)
     xyz, _, _ = synth.make_pair(6, n_beams=32, n_azimuth=900)
     c, _ = OME.sparse_quantize(xyz / np.float32(0.3), return_index=True)
     C = torch.from_numpy(OME.batched_coordinates([c])).to(dev)
@@ -250,6 +284,11 @@ def test_fused_training_path_matches_module_path_and_is_reproducible(dev, monkey
     assert worst < 1e-2, worst          # other summation order in the routed kernels: ReLU kink flips (see the test above)
     for n in ba:
         assert torch.allclose(ba[n].float(), bm[n].float(), rtol=1e-4, atol=1e-6), n
+    # the fused path's gradients at a tight bar: float64 oracle with the first run's ReLU masks pinned
+    assert len(rec.calls) == 2 and len(rec.nodes) == 46
+    Cn = C.cpu().numpy()
+    _fp64_leg(monkeypatch, rec, "ResUNetFatBN", 128, state0, Cn, np.ones((len(Cn), 1), np.float32), ya, ga, ba, proj,
+              calls=rec.calls[:1], tag="FatBN fused")
 
 
 def test_stacked_frames_equal_separate_calls(dev):

@@ -21,74 +21,13 @@ from apr_amd import MinkowskiEngine as ME
 from apr_amd import ops, synth
 from apr_amd.fcgf.model import resunet as RU
 from oracle import me_oracle as OME
-from tests.helpers import model_pair, rel_l2
+from tests.helpers import _LibProxy, _recording_function, model_pair, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 BARS = {"y": 2e-6, "din": 3e-6, "dres": 3e-6, "dW": 5e-6, "dgamma": 3e-6, "dbeta": 4e-7, "dbias": 3e-7,
         "running_mean": 1e-5, "running_var": 2e-6,
         "dbias/|dz|": 5e-6}      # a conv bias ahead of a BatchNorm: |hip - fp64| / |dz| where the fp64 value is 0
-
-# launch entry points of the conv routes (ops.spconv / dense_*): the name of each route
-ROUTES = {"apr_spconv_ws3_fwd_bf3": "ws3", "apr_spconv_ws_fwd_bf3": "ws", "apr_spconv_fwd": "tile",
-          "apr_spconv_os_fwd": "os", "apr_dense_gemm_bf3": "dense", "apr_dense_rows_bf3": "dense"}
-
-
-class _LibProxy:
-    """Stands in for the loaded library behind ops._lib_(): every call is logged by entry-point name."""
-
-    def __init__(self, lib):
-        self._lib = lib
-        self.log = []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not callable(fn):
-            return fn
-
-        def call(*args):
-            self.log.append(name)
-            return fn(*args)
-        return call
-
-
-def _routes(names):
-    return {ROUTES[n] for n in names if n in ROUTES}
-
-
-def _recording_function(nodes, proxy):
-    """ops.ConvBnActFunction that records each node's inputs, outputs, running statistics, gradients and routes."""
-    base = ops.ConvBnActFunction
-
-    def cl(t):
-        return None if t is None else t.detach().clone()
-
-    class Recording(base):
-        @staticmethod
-        def forward(ctx, x, kernel, gamma, beta, bias, residual, cfg):
-            bn = cfg["bn"].bn if cfg["bn"] is not None else None
-            rec = dict(x=cl(x), x_grad=x.requires_grad, kernel=cl(kernel), gamma=cl(gamma), beta=cl(beta), bias=cl(bias),
-                       residual=cl(residual), cfg=cfg)
-            if bn is not None:
-                rec.update(rm=cl(bn.running_mean), rv=cl(bn.running_var), nbt=int(bn.num_batches_tracked))
-            start = len(proxy.log)
-            y = base.forward(ctx, x, kernel, gamma, beta, bias, residual, cfg)
-            rec.update(y=cl(y), fwd=_routes(proxy.log[start:]))
-            if bn is not None:
-                rec.update(rm_after=cl(bn.running_mean), rv_after=cl(bn.running_var), nbt_after=int(bn.num_batches_tracked))
-            ctx.rec = len(nodes)
-            nodes.append(rec)
-            return y
-
-        @staticmethod
-        def backward(ctx, dy):
-            start = len(proxy.log)
-            grads = base.backward(ctx, dy)
-            nodes[ctx.rec].update(dy=cl(dy), grads=[cl(g) for g in grads[:6]], bwd=_routes(proxy.log[start:]))
-            return grads
-
-    return Recording
-
 
 def _ref_unit(rec):
     """float64 rebuild of one recorded node -> (y, mask disagreements, {name: (hip, ref)} of the gradients,
