@@ -227,6 +227,17 @@ PROTOTYPES = {
     "apr_nn3_scratch_bytes": (_sz, [_i64, _i64]),
     "apr_nn3": (C.c_int, [_p, _i64, _p, _i64, C.c_float, _p, _p, _p, _sz, _p]),
     "apr_nn3_batch": (C.c_int, [_p, _p, _p, _p, _i32, C.c_float, _p, _p, _p, _p, _sz, _p]),
+    "apr_overlap_labels": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    "apr_weighted_bce_scratch_bytes": (_sz, []),
+    "apr_weighted_bce_forward": (C.c_int, [_p, _p, _i64, _p, _p, _p, _sz, _p]),
+    "apr_weighted_bce_backward": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "apr_gathered_argmax": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "apr_saliency_labels": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p]),
+    "apr_circle_select": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _f32, _p, _p, _p]),
+    "apr_circle_gather": (C.c_int, [_p, _p, _p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "apr_circle_forward": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "apr_circle_backward": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "apr_circle_scatter": (C.c_int, [_p, _p, _i32, _i32, _p, _i64, _p]),
 }
 
 class KpResnetDesc(C.Structure):

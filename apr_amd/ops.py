@@ -1247,6 +1247,183 @@ def feature_nn(f0, f1, return_distance=False, impl=None):
     return (idx, d2) if return_distance else idx
 
 
+# ----------------------------------------------------------------------------
+# descriptor loss of Predator_APR (lib/loss.py:16-178; csrc/metric_loss.hip).  None of these synchronises.
+# ----------------------------------------------------------------------------
+
+def _dev(t, dtype, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype:
+        raise _lib.AprHipError(f"{name}: need a {dtype} GPU tensor (no CPU fallback), got "
+                               f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', 'the host')}")
+    return t.contiguous()
+
+
+def overlap_labels(correspondence, n_src, n_tgt):
+    """loss.py:114-123 -> (gt f32 [n_src + n_tgt], src_idx i32 [n_src], tgt_idx i32 [n_tgt], counts i32 [3] on the device).
+    The index lists are ascending; only their first counts[0] / counts[1] entries are meaningful."""
+    corr = _dev(correspondence, torch.int64, "overlap_labels.correspondence")
+    dev = corr.device
+    gt = torch.empty(n_src + n_tgt, dtype=torch.float32, device=dev)
+    src_idx = torch.empty(n_src, dtype=torch.int32, device=dev)
+    tgt_idx = torch.empty(n_tgt, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    check(_lib_().apr_overlap_labels(ptr(corr), corr.shape[0], n_src, n_tgt, ptr(gt), ptr(src_idx), ptr(tgt_idx), ptr(counts),
+                                     stream()))
+    return gt, src_idx, tgt_idx, counts
+
+
+def weighted_bce(pred, gt, n_dev=None):
+    """get_weighted_bce_loss (loss.py:79-97) -> f32 [8]: loss, w_negative, precision, recall, tp, fp, fn, n.  `n_dev`: a
+    device int32 count that shortens the vectors (the gathered saliency scores)."""
+    pred, gt = _dev(pred, torch.float32, "weighted_bce.pred"), _dev(gt, torch.float32, "weighted_bce.gt")
+    if pred.dim() != 1 or pred.shape != gt.shape:
+        raise _lib.AprHipError("weighted_bce: prediction and gt must be vectors of one length")
+    lib = _lib_()
+    sb = int(lib.apr_weighted_bce_scratch_bytes())
+    scratch = torch.empty(sb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty(8, dtype=torch.float32, device=pred.device)
+    check(lib.apr_weighted_bce_forward(ptr(pred), ptr(gt), pred.shape[0], ptr(n_dev), ptr(out), ptr(scratch), sb, stream()))
+    return out
+
+
+def weighted_bce_backward(pred, gt, out8, grad_out, n_dev=None, scatter_pos=None, dpred=None):
+    """d loss / d pred; with `scatter_pos` the entries land at those positions of `dpred` (zeroed by the caller)."""
+    pred, gt = _dev(pred, torch.float32, "weighted_bce_backward.pred"), _dev(gt, torch.float32, "weighted_bce_backward.gt")
+    out8, grad_out = _dev(out8, torch.float32, "weighted_bce_backward.out8"), _dev(grad_out, torch.float32, "weighted_bce_backward.grad_out")
+    if dpred is None:
+        dpred = torch.zeros_like(pred)
+    check(_lib_().apr_weighted_bce_backward(ptr(pred), ptr(gt), pred.shape[0], ptr(n_dev), ptr(out8), ptr(grad_out),
+                                            ptr(scatter_pos), ptr(dpred), stream()))
+    return dpred
+
+
+def gathered_argmax(a, a_idx, na_dev, b, b_idx, nb_dev):
+    """Row and column arg-max of a[a_idx] @ b[b_idx].T (loss.py:132-138) without the matrix -> (row_arg, col_arg) i32,
+    positions in the index lists, ties to the lowest.  a_idx / b_idx: i32 lists whose device-side lengths are na_dev /
+    nb_dev."""
+    a, b = _dev(a, torch.float32, "gathered_argmax.a"), _dev(b, torch.float32, "gathered_argmax.b")
+    a_idx, b_idx = _dev(a_idx, torch.int32, "gathered_argmax.a_idx"), _dev(b_idx, torch.int32, "gathered_argmax.b_idx")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise _lib.AprHipError("gathered_argmax: channel mismatch")
+    row_arg = torch.zeros(a_idx.shape[0], dtype=torch.int32, device=a.device)
+    col_arg = torch.zeros(b_idx.shape[0], dtype=torch.int32, device=a.device)
+    check(_lib_().apr_gathered_argmax(ptr(a), ptr(a_idx), ptr(na_dev), a_idx.shape[0], ptr(b), ptr(b_idx), ptr(nb_dev),
+                                      b_idx.shape[0], a.shape[1], ptr(row_arg), ptr(col_arg), stream()))
+    return row_arg, col_arg
+
+
+def saliency_labels(src_pcd, tgt_pcd, rot, trans, src_idx, tgt_idx, counts, row_arg, col_arg, scores_saliency, radius):
+    """loss.py:136-144 -> (labels f32, gathered scores f32, their positions i32, partner distance f32), each
+    [n_src + n_tgt] with counts[2] meaningful entries (src list, then tgt list)."""
+    src_pcd, tgt_pcd = _dev(src_pcd, torch.float32, "saliency_labels.src_pcd"), _dev(tgt_pcd, torch.float32, "saliency_labels.tgt_pcd")
+    rot, trans = _dev(rot, torch.float32, "saliency_labels.rot"), _dev(trans, torch.float32, "saliency_labels.trans")
+    scores_saliency = _dev(scores_saliency, torch.float32, "saliency_labels.scores_saliency")
+    for name, t in (("src_idx", src_idx), ("tgt_idx", tgt_idx), ("counts", counts), ("row_arg", row_arg), ("col_arg", col_arg)):
+        _dev(t, torch.int32, "saliency_labels." + name)
+    n_src, n_tgt = src_pcd.shape[0], tgt_pcd.shape[0]
+    if scores_saliency.shape[0] != n_src + n_tgt or src_idx.shape[0] != n_src or tgt_idx.shape[0] != n_tgt:
+        raise _lib.AprHipError("saliency_labels: vector lengths do not match the clouds")
+    dev = src_pcd.device
+    # zeros / halves: the tail past counts[2] is never read by the kernels but stays a valid probability
+    labels = torch.zeros(n_src + n_tgt, dtype=torch.float32, device=dev)
+    sel = torch.full((n_src + n_tgt,), 0.5, dtype=torch.float32, device=dev)
+    pos = torch.zeros(n_src + n_tgt, dtype=torch.int32, device=dev)
+    dist = torch.zeros(n_src + n_tgt, dtype=torch.float32, device=dev)
+    check(_lib_().apr_saliency_labels(ptr(src_pcd), ptr(tgt_pcd), ptr(rot), ptr(trans), ptr(src_idx), ptr(tgt_idx),
+                                      ptr(counts), ptr(row_arg), ptr(col_arg), ptr(scores_saliency), n_src, n_tgt,
+                                      float(radius), ptr(labels), ptr(sel), ptr(pos), ptr(dist), stream()))
+    return labels, sel, pos, dist
+
+
+def circle_select(correspondence, src_pcd, tgt_pcd, rot, trans, thresh):
+    """loss.py:153-155 -> (filt i32 [C]: rows of `correspondence` closer than thresh, in order; count i32 [1] on the device)."""
+    corr = _dev(correspondence, torch.int64, "circle_select.correspondence")
+    src_pcd, tgt_pcd = _dev(src_pcd, torch.float32, "circle_select.src_pcd"), _dev(tgt_pcd, torch.float32, "circle_select.tgt_pcd")
+    rot, trans = _dev(rot, torch.float32, "circle_select.rot"), _dev(trans, torch.float32, "circle_select.trans")
+    filt = torch.empty(max(int(corr.shape[0]), 1), dtype=torch.int32, device=corr.device)
+    count = torch.empty(1, dtype=torch.int32, device=corr.device)
+    check(_lib_().apr_circle_select(ptr(corr), corr.shape[0], ptr(src_pcd), src_pcd.shape[0], ptr(tgt_pcd), tgt_pcd.shape[0],
+                                    ptr(rot), ptr(trans), float(thresh), ptr(filt), ptr(count), stream()))
+    return filt, count
+
+
+def circle_gather(correspondence, filt, count, choice, src_pcd, tgt_pcd, src_feats, tgt_feats, rot, trans):
+    """loss.py:156-162 -> dict of the anchors: a_row / b_row i32 [P] (-1: absent), a_pts / b_pts [P,3], a_feats / b_feats
+    [P,D]."""
+    correspondence, choice = _dev(correspondence, torch.int64, "circle_gather.correspondence"), _dev(choice, torch.int64, "circle_gather.choice")
+    filt, count = _dev(filt, torch.int32, "circle_gather.filt"), _dev(count, torch.int32, "circle_gather.count")
+    src_pcd, tgt_pcd = _dev(src_pcd, torch.float32, "circle_gather.src_pcd"), _dev(tgt_pcd, torch.float32, "circle_gather.tgt_pcd")
+    src_feats, tgt_feats = _dev(src_feats, torch.float32, "circle_gather.src_feats"), _dev(tgt_feats, torch.float32, "circle_gather.tgt_feats")
+    rot, trans = _dev(rot, torch.float32, "circle_gather.rot"), _dev(trans, torch.float32, "circle_gather.trans")
+    P, D, dev = int(choice.shape[0]), int(src_feats.shape[1]), src_feats.device
+    g = {"a_row": torch.empty(P, dtype=torch.int32, device=dev), "b_row": torch.empty(P, dtype=torch.int32, device=dev),
+         "a_pts": torch.empty((P, 3), dtype=torch.float32, device=dev), "b_pts": torch.empty((P, 3), dtype=torch.float32, device=dev),
+         "a_feats": torch.empty((P, D), dtype=torch.float32, device=dev),
+         "b_feats": torch.empty((P, D), dtype=torch.float32, device=dev)}
+    check(_lib_().apr_circle_gather(ptr(correspondence), ptr(filt), ptr(count), ptr(choice), P, ptr(src_pcd), ptr(tgt_pcd),
+                                    ptr(src_feats), ptr(tgt_feats), D, ptr(rot), ptr(trans), ptr(g["a_row"]), ptr(g["b_row"]),
+                                    ptr(g["a_pts"]), ptr(g["b_pts"]), ptr(g["a_feats"]), ptr(g["b_feats"]), stream()))
+    return g
+
+
+def _circle_params(params):
+    return (C.c_float * 7)(*[float(v) for v in params])
+
+
+def circle_forward(params, anchors=None, coords_dist=None, feats_dist=None):
+    """get_circle_loss + get_recall (loss.py:34-77) on gathered anchors (`circle_gather`) or on the two dense [na, nb]
+    matrices -> (out4 f32: circle_loss, recall, #row_sel, #col_sel; st_a; st_b; nn i32 [na] = row arg-min of feats_dist).
+    params = (pos_radius, safe_radius, pos_optimal, neg_optimal, pos_margin, neg_margin, log_scale)."""
+    g = anchors or {}
+    for name, t in list(g.items()) + [("coords_dist", coords_dist), ("feats_dist", feats_dist)]:
+        if t is not None and name in ("a_row", "b_row", "a_pts", "b_pts", "a_feats", "b_feats", "coords_dist", "feats_dist"):
+            _dev(t, torch.int32 if name.endswith("_row") else torch.float32, "circle_forward." + name)
+    if anchors is None and (coords_dist is None or feats_dist is None or coords_dist.shape != feats_dist.shape):
+        raise _lib.AprHipError("circle_forward: give the anchors or two distance matrices of one shape")
+    if anchors is not None:
+        na = nb = int(g["a_row"].shape[0])
+        dev = g["a_row"].device
+    else:
+        na, nb = (int(v) for v in coords_dist.shape)
+        dev = coords_dist.device
+    st_a = torch.empty((na, 8), dtype=torch.float32, device=dev)
+    st_b = torch.empty((nb, 8), dtype=torch.float32, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    nn = torch.empty(na, dtype=torch.int32, device=dev)
+    check(_lib_().apr_circle_forward(ptr(g.get("a_feats")), ptr(g.get("a_pts")), ptr(g.get("a_row")), na, ptr(g.get("b_feats")),
+                                     ptr(g.get("b_pts")), ptr(g.get("b_row")), nb, ptr(coords_dist), ptr(feats_dist),
+                                     _circle_params(params), ptr(st_a), ptr(st_b), ptr(out), ptr(nn), stream()))
+    return out, st_a, st_b, nn
+
+
+def circle_backward(params, st_a, st_b, out4, grad_out, anchors=None, coords_dist=None, feats_dist=None):
+    """-> (d a_feats, d b_feats) of the anchors, or d feats_dist for dense inputs."""
+    g = anchors or {}
+    for name, t in (("st_a", st_a), ("st_b", st_b), ("out4", out4), ("grad_out", grad_out)):
+        _dev(t, torch.float32, "circle_backward." + name)
+    grad_out = grad_out.contiguous()
+    na, nb = int(st_a.shape[0]), int(st_b.shape[0])
+    d_a = d_b = d_fd = None
+    if anchors is not None:
+        d_a, d_b = torch.empty_like(g["a_feats"]), torch.empty_like(g["b_feats"])
+    else:
+        d_fd = torch.empty_like(feats_dist)
+    check(_lib_().apr_circle_backward(ptr(g.get("a_feats")), ptr(g.get("a_pts")), ptr(g.get("a_row")), na, ptr(g.get("b_feats")),
+                                      ptr(g.get("b_pts")), ptr(g.get("b_row")), nb, ptr(coords_dist), ptr(feats_dist),
+                                      _circle_params(params), ptr(st_a), ptr(st_b), ptr(out4), ptr(grad_out), ptr(d_a), ptr(d_b),
+                                      ptr(d_fd), stream()))
+    return (d_a, d_b) if anchors is not None else d_fd
+
+
+def circle_scatter(d_anchor, row, n_rows):
+    """Anchor gradients back to the full [n_rows, D] rows; anchors that share a row add in ascending anchor order."""
+    d_anchor, row = _dev(d_anchor, torch.float32, "circle_scatter.d_anchor"), _dev(row, torch.int32, "circle_scatter.row")
+    P, D = d_anchor.shape
+    out = torch.zeros((n_rows, D), dtype=torch.float32, device=d_anchor.device)
+    check(_lib_().apr_circle_scatter(ptr(d_anchor), ptr(row), P, D, ptr(out), n_rows, stream()))
+    return out
+
+
 def ransac_pose(xyz0, xyz1, corr, max_dist, edge_ratio=0.9, max_iter=4000000, seed=0):
     """GPU RANSAC + Kabsch.  Returns (T float64 [4,4] numpy, info dict).  Synchronises."""
     xyz0 = _f32(xyz0, "ransac.xyz0").contiguous()

@@ -925,6 +925,78 @@ int apr_nn3_batch(const float* a, const int64_t* a_offsets_host, const float* b,
                   float cell, uint64_t* out_packed, double* sums_dev, const double* sum_scale_host, void* scratch,
                   size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Predator_APR's descriptor loss, MetricLoss (Predator_APR/lib/loss.py:16-178).  Deterministic: no float atomics,
+ * fixed reduction order, the same bits run to run.  Nothing is sized by (#src rows) x (#tgt rows).
+ * ---------------------------------------------------------------------- */
+
+/* loss.py:114-123.  corr i64[n_corr,2].  gt f32[n_src + n_tgt] = the 0/1 overlap labels (src part, then tgt part);
+ * src_idx i32[n_src] / tgt_idx i32[n_tgt] = the unique first / second columns of corr in ASCENDING order (the reference
+ * takes them from a Python set, whose order is unspecified); counts3 i32[3] on the device = #src_idx, #tgt_idx, their sum. */
+int apr_overlap_labels(const int64_t* corr, int64_t n_corr, int64_t n_src, int64_t n_tgt, float* gt, int32_t* src_idx,
+                       int32_t* tgt_idx, int32_t* counts3, void* stream);
+
+/* loss.py:79-97, get_weighted_bce_loss.  pred / gt f32[n]; n_dev (may be NULL): device count that replaces n when it is
+ * smaller.  out8 f32[8] = loss, w_negative, precision, recall, tp, fp, fn, n.  Each log is clamped at -100 (nn.BCELoss),
+ * round() is half-to-even (0.5 predicts 0), a zero denominator gives precision / recall 0 (sklearn). */
+size_t apr_weighted_bce_scratch_bytes(void);
+int apr_weighted_bce_forward(const float* pred, const float* gt, int64_t n, const int32_t* n_dev, float* out8, void* scratch,
+                             size_t scratch_bytes, void* stream);
+/* d loss / d pred = grad_out[0] * w_i / n * (p - g) / max((1 - p) p, 1e-12), written to dpred[i], or to
+ * dpred[scatter_pos[i]] when scatter_pos is given (the gather of loss.py:142-144 undone; positions are unique). */
+int apr_weighted_bce_backward(const float* pred, const float* gt, int64_t n, const int32_t* n_dev, const float* out8,
+                              const float* grad_out, const int32_t* scatter_pos, float* dpred, void* stream);
+
+/* loss.py:132-138: for scores = a[a_idx] @ b[b_idx].T (never formed) row_arg i32[na] = arg-max along each row and
+ * col_arg i32[nb] = arg-max along each column, as positions in the index lists; ties go to the lowest position.
+ * *na_dev / *nb_dev: device-side list lengths (<= na_max / nb_max, which size the grids); neither may be NULL.  Every
+ * listed index must be a row of its matrix (the lists apr_overlap_labels writes are): the entry point does not know the
+ * row counts and does not check.  d must be 32; exact fp32 (v_mfma_f32_16x16x4_f32). */
+int apr_gathered_argmax(const float* a, const int32_t* a_idx, const int32_t* na_dev, int64_t na_max, const float* b,
+                        const int32_t* b_idx, const int32_t* nb_dev, int64_t nb_max, int32_t d, int32_t* row_arg,
+                        int32_t* col_arg, void* stream);
+
+/* loss.py:136-144: dist[i] = |rot src + trans - tgt| between every listed point and its arg-max partner (src list, then
+ * tgt list), labels = dist < radius, sel_scores = scores_saliency at the listed points, pos = their position in
+ * scores_saliency [n_src + n_tgt]. */
+int apr_saliency_labels(const float* src_pcd, const float* tgt_pcd, const float* rot9, const float* trans3,
+                        const int32_t* src_idx, const int32_t* tgt_idx, const int32_t* counts3, const int32_t* row_arg,
+                        const int32_t* col_arg, const float* scores_saliency, int64_t n_src, int64_t n_tgt, float radius,
+                        float* labels, float* sel_scores, int32_t* pos, float* dist, void* stream);
+
+/* loss.py:153-155: filt i32[<= n_corr] = the rows of corr with |rot src + trans - tgt| < thresh, in order; *count on
+ * the device. */
+int apr_circle_select(const int64_t* corr, int64_t n_corr, const float* src_pcd, int64_t n_src, const float* tgt_pcd,
+                      int64_t n_tgt, const float* rot9, const float* trans3, float thresh, int32_t* filt, int32_t* count,
+                      void* stream);
+
+/* loss.py:156-162: anchor k = corr[filt[choice[k]]], k < p <= 512: rows (a_row / b_row, -1 where choice[k] is outside the
+ * filtered list: an absent anchor), transformed src point / tgt point, the two feature rows (d == 32). */
+int apr_circle_gather(const int64_t* corr, const int32_t* filt, const int32_t* count, const int64_t* choice, int32_t p,
+                      const float* src_pcd, const float* tgt_pcd, const float* src_feats, const float* tgt_feats, int32_t d,
+                      const float* rot9, const float* trans3, int32_t* a_row, int32_t* b_row, float* a_pts, float* b_pts,
+                      float* a_feats, float* b_feats, void* stream);
+
+/* loss.py:34-77 (get_circle_loss, get_recall) and :166-167.  Either the gathered anchors (coords_dist == NULL), from
+ * which both distance matrices are formed on the fly, sqrt(clamp(., 1e-12)) as lib/utils.py:78-98, or the two dense
+ * [na, nb] matrices themselves.  params_host f32[7] = pos_radius, safe_radius, pos_optimal, neg_optimal, pos_margin,
+ * neg_margin, log_scale.  st_a f32[na,8] / st_b f32[nb,8]: per-row / per-column records the backward reads.  out4 =
+ * circle_loss, recall, #row_sel, #col_sel; an empty selection gives NaN as mean() of nothing.  nn i32[na] (may be
+ * NULL): arg-min of feats_dist along each row.  na, nb <= 512. */
+int apr_circle_forward(const float* a_feats, const float* a_pts, const int32_t* a_row, int32_t na, const float* b_feats,
+                       const float* b_pts, const int32_t* b_row, int32_t nb, const float* coords_dist,
+                       const float* feats_dist, const float* params_host, float* st_a, float* st_b, float* out4, int32_t* nn,
+                       void* stream);
+/* d circle_loss / d a_feats, d b_feats (anchors; zero gradient where the 1e-12 clamp binds), or / d feats_dist (dense). */
+int apr_circle_backward(const float* a_feats, const float* a_pts, const int32_t* a_row, int32_t na, const float* b_feats,
+                        const float* b_pts, const int32_t* b_row, int32_t nb, const float* coords_dist,
+                        const float* feats_dist, const float* params_host, const float* st_a, const float* st_b,
+                        const float* out4, const float* grad_out, float* d_a, float* d_b, float* d_feats_dist, void* stream);
+/* d_full[row[k]] = sum of d_anchor[k'] over the anchors k' that share the row, in ascending k' (loss.py:161-162 undone);
+ * rows that no anchor names are left as they are (zero them first). */
+int apr_circle_scatter(const float* d_anchor, const int32_t* row, int32_t p, int32_t d, float* d_full, int64_t n_rows,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
