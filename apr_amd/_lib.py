@@ -180,6 +180,8 @@ PROTOTYPES = {
     "apr_match_pose_batch_enqueue": (C.c_int, [_p, _i32, _i32, C.c_double, C.c_double, _i64, _p, _sz, _p, _p]),
     "apr_match_pose_batch_finish": (C.c_int, [_p, _i32, _i32, C.c_double, C.c_double, _i64, _p, _sz, _p, _p, _p]),
     "apr_irls_scratch_bytes": (_sz, [_i64]),
+    "apr_valid_pair": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _f32, _p, _i64, _i64, _p, _sz, _p]),
+    "apr_valid_pair_scratch_bytes": (_sz, [_i64]),
     "apr_contrastive_reduce": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _f32, _f32, _p, _p]),
     "apr_grid_subsample_scratch_bytes": (_sz, [_i64]),
     "apr_grid_subsample": (C.c_int, [_p, _i64, _p, _i32, _f32, _p, _i32, _p, _p, _p, _p, _sz, _p]),

@@ -1712,3 +1712,35 @@ def irls_pose(pts0, pts1, weight=None):
     T = (C.c_float * 16)()
     check(lib.apr_irls_pose(ptr(pts0), ptr(pts1), ptr(weight), n, T, ptr(scratch), sb, stream()))
     return torch.tensor(list(T), dtype=torch.float32).view(4, 4)
+
+
+VALID_RECORD_FLOATS = 24      # APR_VALID_RECORD_FLOATS
+# columns of a validation record (include/apr_hip.h: apr_valid_pair)
+VALID_CORR_DIST, VALID_RTE, VALID_RRE, VALID_HIT_RATIO, VALID_N_CORR, VALID_T_EST = 0, 1, 2, 3, 4, 5
+VALID_CHAMFER, VALID_REG, VALID_N_HIT = 21, 22, 23
+
+
+def valid_pair(xyz0, xyz1, nn, T_gt, records, slot, sel0=None, sel1=None, hit_thresh=0.1):
+    """Matching metrics of one validation pair into `records[slot]` (float32 [pairs, 24] on the GPU): correspondences
+    xyz0[sel0] <-> xyz1[sel1[nn]], est_quad_linear_robust on them, corr_dist, rte, rre, hit ratio (apr_valid_pair).
+    One launch; does not synchronise and returns nothing -- read `records` back when the epoch is over."""
+    xyz0 = _f32(xyz0, "valid_pair.xyz0").contiguous()
+    xyz1 = _f32(xyz1, "valid_pair.xyz1").contiguous()
+    T_gt = _f32(T_gt, "valid_pair.T_gt").contiguous()
+    if T_gt.numel() != 16:
+        raise _lib.AprHipError("valid_pair: T_gt must hold 16 floats")
+    _lib.require_gpu_tensor(records, torch.float32, "valid_pair.records")
+    if records.dim() != 2 or records.shape[1] != VALID_RECORD_FLOATS:
+        raise _lib.AprHipError(f"valid_pair: records must be [pairs, {VALID_RECORD_FLOATS}]")
+    idx = [None if t is None else _lib.require_gpu_tensor(t, torch.int64, name)
+           for t, name in ((sel0, "valid_pair.sel0"), (sel1, "valid_pair.sel1"), (nn, "valid_pair.nn"))]
+    m0 = xyz0.shape[0] if sel0 is None else sel0.shape[0]
+    m1 = xyz1.shape[0] if sel1 is None else sel1.shape[0]
+    if nn.shape[0] != m0:
+        raise _lib.AprHipError(f"valid_pair: nn has {nn.shape[0]} rows for {m0} source rows")
+    lib = _lib_()
+    sb = int(lib.apr_valid_pair_scratch_bytes(m0))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=xyz0.device)
+    check(lib.apr_valid_pair(ptr(xyz0), xyz0.shape[0], ptr(xyz1), xyz1.shape[0], ptr(idx[0]), ptr(idx[1]), m0, m1,
+                             ptr(idx[2]), ptr(T_gt), float(hit_thresh), ptr(records), records.shape[0], int(slot),
+                             ptr(scratch), sb, stream()))

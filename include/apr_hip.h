@@ -613,6 +613,29 @@ int apr_irls_pose(const float* pts0, const float* pts1, const float* weight, int
                   float* T_host, void* scratch, size_t scratch_bytes, void* stream);
 size_t apr_irls_scratch_bytes(int64_t n);
 
+/* Matching metrics of one validation pair, replaces the host-chained statements of
+ *   GenerativePairTrainer._valid_epoch (FCGF_APR/lib/complement_trainer.py:555-572): find_corr's gathers,
+ *   est_quad_linear_robust, corr_dist, rte, rre, evaluate_hit_ratio (lib/trainer.py:392-395).
+ * One launch of one persistent workgroup, nothing synchronises, every result stays on the device:
+ *   xyz0 f32[n0,3], xyz1 f32[n1,3]: the clouds (the collate's pcd0[0], pcd1[0]);
+ *   sel0 i64[m0], sel1 i64[m1]: find_corr's subsample rows, NULL = every row (then m0 == n0 / m1 == n1);
+ *   nn i64[m0]: feature nearest neighbour of subsampled source row i among the m1 subsampled target rows;
+ *   T_gt f32[16] row-major ground truth; hit_thresh: config.hit_ratio_thresh.
+ * Writes record `slot` of records f32[n_slots, APR_VALID_RECORD_FLOATS]:
+ *   [0] corr_dist = mean over ALL n0 rows of min(|T_est x - T_gt x|, 1)      [1] rte = |t_est - t_gt|
+ *   [2] rre = arccos((trace(R_est^T R_gt) - 1) / 2) in radians, NaN when the argument leaves [-1, 1] (as NumPy)
+ *   [3] hit_ratio = share of the m0 correspondences with sqrt(|T_gt x0 - x1|^2 + 1e-6) < hit_thresh
+ *   [4] n_corr = m0, or MINUS the number of sel0 / sel1 / nn entries out of range (those read row 0)
+ *   [5..20] T_est row-major, the bits apr_irls_pose gives on the same correspondences
+ *   [21], [22] left untouched for the caller (the NPR validation terms)       [23] hit count.
+ * Sums run in a fixed order (no float atomics): the same bits on every run. */
+#define APR_VALID_RECORD_FLOATS 24
+int apr_valid_pair(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int64_t* sel0,
+                   const int64_t* sel1, int64_t m0, int64_t m1, const int64_t* nn, const float* T_gt,
+                   float hit_thresh, float* records, int64_t n_slots, int64_t slot, void* scratch,
+                   size_t scratch_bytes, void* stream);
+size_t apr_valid_pair_scratch_bytes(int64_t m0);
+
 /* Hardest-contrastive mining (forward), replaces the mining + masking + loss arithmetic of
  *   contrastive_hardest_negative_loss (FCGF_APR/lib/trainer.py:400-452, `_hash` util/misc.py:6-18).
  *   pos_f0/pos_f1 f32[p,c]: features of the sampled positive pairs; nn01/nn10 u64[p]: packed

@@ -1,0 +1,47 @@
+"""Train on synthetic pairs, validate and register held-out ones with the learned features (apr_amd/fcgf/lib/learned.py);
+prints one JSON line.
+
+    python scripts/trained_synthetic.py [--train 8] [--val 8] [--iterations 300] [--k 1] [--model ResUNetFatBN] [--n-out 128]
+
+The defaults are what fits about two minutes on one MI355X: most of it is the host ray-casting the scans (two key frames
+and 4k complement scans per pair), not the GPU.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from apr_amd.fcgf.lib.learned import train_and_validate  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--train", type=int, default=8)
+    ap.add_argument("--val", type=int, default=8)
+    ap.add_argument("--iterations", type=int, default=300)
+    ap.add_argument("--k", type=int, default=1, help="complement scans on each side of a key frame (the trainer uses 5)")
+    ap.add_argument("--model", default="ResUNetFatBN")
+    ap.add_argument("--n-out", type=int, default=128)
+    ap.add_argument("--beams", type=int, default=64)
+    ap.add_argument("--azimuth", type=int, default=1875)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ransac-iters", type=int, default=200000)
+    a = ap.parse_args()
+    r = train_and_validate(torch.device("cuda:0"), a.train, a.val, a.iterations, model=a.model, n_out=a.n_out,
+                           n_beams=a.beams, n_azimuth=a.azimuth, seed=a.seed, k=a.k, ransac_iters=a.ransac_iters)
+    line = {"pairs_train": a.train, "pairs_val": a.val, "iterations": a.iterations, "model": a.model, "n_out": a.n_out,
+            "rays": [a.beams, a.azimuth], "complement_scans_per_frame": 2 * a.k, "voxels_val_mean": sum(r["voxels"]) / len(r["voxels"]),
+            "valid_before": r["valid_before"], "valid_after": r["valid_after"],
+            "loss_first_last": [r["losses"][0], r["losses"][-1]] if r["losses"] else None,
+            "recall_rte2m_rre5deg": r["recall"], "rte_success_m": r["rte_success"], "rre_success_deg": r["rre_success"],
+            "mean_valid_hypotheses": r["mean_valid_hypotheses"], "ransac_iters": r["ransac_iters"],
+            "seconds": {k: round(v, 2) for k, v in r["seconds"].items()}}
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
