@@ -240,6 +240,8 @@ PROTOTYPES = {
     "apr_circle_forward": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "apr_circle_backward": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "apr_circle_scatter": (C.c_int, [_p, _p, _i32, _i32, _p, _i64, _p]),
+    "apr_icp_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "apr_icp_batch": (C.c_int, [_p, _p, _p, _p, _i32, _p, _i32, _p, _f64, _i32, _f64, _f64, _p, _p, _p, _sz, _p]),
 }
 
 class KpResnetDesc(C.Structure):

@@ -2,6 +2,8 @@
 
   aggregate_frames   <- FCGF_APR/lib/complement_data_loader.py:576-628,671-674 (transform the 2k complement
                         frames into the key frame, crop to the key frame's radius, voxel-quantise)
+  refine_pose / refine_complement_poses <- complement_data_loader.py:369-405 (_get_icp, _get_neighbourhood_icp: the
+                        odometry pose of every complement frame goes through point-to-point ICP first)
   get_matching_indices <- FCGF_APR/util/pointcloud.py:53-66 ; Predator_APR/lib/benchmark_utils.py:121-135
   chamfer_distance   <- FCGF_APR/lib/complement_trainer.py:188-196 (chamferdist 1-NN sums, both directions)
   GenerativeMLP*     <- FCGF_APR/model/mlp.py:6-37 (same module / parameter names: `mlp.0.weight` ...)
@@ -51,8 +53,57 @@ def crop_to_radius(key_xyz, pts):
     return out[: int(cnt.item())]
 
 
-def aggregate_frames(key_xyz, complement_xyz, complement_poses, voxel_size):
-    """APG: returns (xyz_nghb cropped [M,3], sel indices of its voxelised subset)."""
+def voxel_first_rows(clouds, voxel_size):
+    """Per cloud, the rows of ME.utils.sparse_quantize(xyz / voxel_size, return_index=True): the FIRST row of every occupied
+    voxel, ascending (int64 on the GPU).  One host synchronisation for all the row counts."""
+    maps = [ops.build_map(ops.voxelize(x, voxel_size, 0), want_first=True) for x in clouds]
+    ops.finalize_maps(maps)
+    return [torch.sort(m.first[: m.n]).values for m in maps]
+
+
+def refine_complement_poses(xyz_curr, xyz_cmpls, Ms, icp_voxel_size=0.05, max_dist=0.2, max_iteration=200,
+                            relative_fitness=1e-6, relative_rmse=1e-6, return_results=False):
+    """_get_neighbourhood_icp (complement_data_loader.py:401-405) as ONE apr_icp_batch call with the key frame as the shared
+    target.  Per complement frame, _get_icp's recipe (:376-388): both clouds reduced to the first row of every
+    `icp_voxel_size` voxel, the odometry pose M applied to the frame (pts @ R.T + t in float32, :65-70), ICP of the moved
+    frame onto the key frame from the identity with open3d's default thresholds, and the two poses composed.
+    icp_voxel_size=None skips the reduction (Predator_APR's loader registers the full clouds).
+
+    The composition returned is reg.transformation @ M in the column-vector form every consumer here uses
+    (apply_transform, aggregate_frames): M first, then ICP's correction, i.e. the pose ICP actually found.  The reference
+    writes `M @ reg.transformation` (:388) on transforms it handles transposed (:379-380); the two agree wherever the
+    correction commutes with M, which is the reference's regime (a correction of millimetres).
+
+    -> list of float64 [4,4] numpy poses (and the RegistrationResults when return_results)."""
+    from .. import registration
+    clouds = [_f32(xyz_curr)] + [_f32(x) for x in xyz_cmpls]
+    if icp_voxel_size is not None:
+        clouds = [x[sel].contiguous() for x, sel in zip(clouds, voxel_first_rows(clouds, icp_voxel_size))]
+    tgt = clouds[0]
+    Ms = [np.asarray(M, dtype=np.float64) for M in Ms]
+    moved = [apply_transform(x, M) for x, M in zip(clouds[1:], Ms)]
+    off = np.concatenate([[0], np.cumsum([len(m) for m in moved])]).astype(np.int64)
+    nb = len(moved)
+    rec, _ = ops.icp_batch(torch.cat(moved, 0), off, tgt, [0, len(tgt)], np.tile(np.eye(4), (nb, 1, 1)), max_dist,
+                           max_iteration, relative_fitness, relative_rmse, tgt_of_problem=[0] * nb)
+    results = registration.icp_results(rec)
+    poses = [r.transformation @ M for r, M in zip(results, Ms)]
+    return (poses, results) if return_results else poses
+
+
+def refine_pose(xyz_curr, xyz_next, M, icp_voxel_size=0.05, max_dist=0.2, max_iteration=200):
+    """_get_icp (complement_data_loader.py:369-399) without its disk cache: `next` registered onto `curr`, starting from
+    the odometry pose M.  -> float64 [4,4] numpy (see refine_complement_poses)."""
+    return refine_complement_poses(xyz_curr, [xyz_next], [M], icp_voxel_size, max_dist, max_iteration)[0]
+
+
+def aggregate_frames(key_xyz, complement_xyz, complement_poses, voxel_size, refine=False, icp_voxel_size=0.05,
+                     icp_max_dist=0.2, icp_max_iteration=200):
+    """APG: returns (xyz_nghb cropped [M,3], sel indices of its voxelised subset).  refine=True: `complement_poses` are raw
+    odometry and go through refine_complement_poses first, as the reference's loader does (:576-590)."""
+    if refine:
+        complement_poses = refine_complement_poses(key_xyz, complement_xyz, complement_poses, icp_voxel_size, icp_max_dist,
+                                                   icp_max_iteration)
     moved = [apply_transform(x, M) for x, M in zip(complement_xyz, complement_poses)]
     nghb = crop_to_radius(key_xyz, torch.cat(moved, 0))
     coords = ops.voxelize(nghb, voxel_size, 0)

@@ -60,3 +60,74 @@ def rte_rre(T_est, T_gt):
     c = (np.trace(T_est[:3, :3].T @ T_gt[:3, :3]) - 1) / 2
     rre = np.degrees(np.arccos(np.clip(c, -1.0, 1.0)))
     return float(rte), float(rre)
+
+
+# ---- point-to-point ICP: the open3d call at FCGF_APR/lib/complement_data_loader.py:384-387 (and data_loaders.py:460-463,
+# Predator_APR/datasets/kitti.py:424-426) on the HIP kernels of csrc/icp.hip.  open3d is absent from this image, so the
+# algorithm is restated from its >= 0.12 sources (RegistrationICP) and parity with it is unpinned.
+
+class TransformationEstimationPointToPoint:
+    """Rotation + translation, no scaling: the only estimation method the HIP kernel implements."""
+
+    def __init__(self, with_scaling=False):
+        if with_scaling:
+            raise NotImplementedError("registration_icp: point-to-point with scaling is not implemented on the HIP path")
+        self.with_scaling = False
+
+
+class ICPConvergenceCriteria:
+    """open3d's defaults; both reference call sites pass max_iteration=200 and keep the two thresholds."""
+
+    def __init__(self, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+        self.relative_fitness = float(relative_fitness)
+        self.relative_rmse = float(relative_rmse)
+        self.max_iteration = int(max_iteration)
+
+
+class RegistrationResult:
+    """transformation float64 [4,4] (target ~= source @ R.T + t), fitness, inlier_rmse, correspondence_set int64 [K,2]
+    (source row, target row); `iterations` is this port's addition."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, correspondence_set, iterations):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.correspondence_set = correspondence_set
+        self.iterations = iterations
+
+    def __repr__(self):
+        return (f"RegistrationResult with fitness={self.fitness:e}, inlier_rmse={self.inlier_rmse:e}, and "
+                f"correspondence_set size of {len(self.correspondence_set)}")
+
+
+def icp_results(rec, corr=None, src_offsets=None):
+    """Records of ops.icp_batch (one device -> host copy) -> list of RegistrationResult."""
+    host = rec.cpu().numpy()
+    corr_host = None if corr is None else corr.cpu().numpy()
+    out = []
+    for i, r in enumerate(host):
+        cs = np.empty((0, 2), dtype=np.int64)
+        if corr_host is not None:
+            c = corr_host[src_offsets[i]:src_offsets[i + 1]]
+            rows = np.nonzero(c >= 0)[0]
+            cs = np.stack([rows, c[rows]], 1).astype(np.int64)
+        out.append(RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[ops.ICP_FITNESS]), float(r[ops.ICP_RMSE]), cs,
+                                      int(r[ops.ICP_ITERATIONS])))
+    return out
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """o3d.pipelines.registration.registration_icp(source, target, max_correspondence_distance, init, estimation_method,
+    criteria) for [N,3] arrays / tensors in place of open3d point clouds.  Synchronises."""
+    if estimation_method is None:
+        estimation_method = TransformationEstimationPointToPoint()
+    if not isinstance(estimation_method, TransformationEstimationPointToPoint):
+        raise NotImplementedError("registration_icp: only TransformationEstimationPointToPoint runs on the HIP kernels "
+                                  f"(got {type(estimation_method).__name__}); point-to-plane ICP is out of scope")
+    if criteria is None:
+        criteria = ICPConvergenceCriteria()
+    src, tgt = _dev(source), _dev(target)
+    init = np.eye(4) if init is None else np.asarray(init, dtype=np.float64)
+    rec, corr = ops.icp_batch(src, [0, len(src)], tgt, [0, len(tgt)], init.reshape(1, 4, 4), max_correspondence_distance,
+                              criteria.max_iteration, criteria.relative_fitness, criteria.relative_rmse, want_corr=True)
+    return icp_results(rec, corr, [0, len(src)])[0]

@@ -1744,3 +1744,48 @@ def valid_pair(xyz0, xyz1, nn, T_gt, records, slot, sel0=None, sel1=None, hit_th
     check(lib.apr_valid_pair(ptr(xyz0), xyz0.shape[0], ptr(xyz1), xyz1.shape[0], ptr(idx[0]), ptr(idx[1]), m0, m1,
                              ptr(idx[2]), ptr(T_gt), float(hit_thresh), ptr(records), records.shape[0], int(slot),
                              ptr(scratch), sb, stream()))
+
+
+ICP_RECORD_DOUBLES = 20       # APR_ICP_RECORD_DOUBLES
+# columns of an ICP record (include/apr_hip.h: apr_icp_batch); [0, 16) is the row-major 4x4 transform
+ICP_FITNESS, ICP_RMSE, ICP_N_CORR, ICP_ITERATIONS = 16, 17, 18, 19
+
+
+def icp_batch(src, src_offsets, tgt, tgt_offsets, init, max_dist, max_iteration=30, relative_fitness=1e-6,
+              relative_rmse=1e-6, tgt_of_problem=None, want_corr=False):
+    """Point-to-point ICP of nb problems in ONE library call (apr_icp_batch; open3d >= 0.12 registration_icp).
+
+    src f32 [sum n, 3] / tgt f32 [sum m, 3] on the GPU, `src_offsets` [nb + 1] and `tgt_offsets` [segments + 1] host row
+    offsets; problem i registers its source rows onto target segment `tgt_of_problem[i]` (default: segment i), so many
+    problems may share one target.  init: float64 [nb, 4, 4] (GPU tensor or array).
+    -> (records float64 [nb, 20] on the GPU: T[16], fitness, inlier_rmse, #correspondences, iterations;
+        corr int32 [sum n] on the GPU -- the target row of every source row inside its segment, or -1 -- or None)."""
+    src = _f32(src, "icp_batch.src").contiguous()
+    tgt = _f32(tgt, "icp_batch.tgt").contiguous()
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.dim() != 2 or tgt.shape[1] != 3:
+        raise _lib.AprHipError("icp_batch: src and tgt must be [rows, 3]")
+    so = np.ascontiguousarray(np.asarray(src_offsets, dtype=np.int64))
+    to = np.ascontiguousarray(np.asarray(tgt_offsets, dtype=np.int64))
+    nb, n_tgt = len(so) - 1, len(to) - 1
+    if nb < 1 or n_tgt < 1 or so[-1] != src.shape[0] or to[-1] != tgt.shape[0]:
+        raise _lib.AprHipError("icp_batch: the offsets must cover the rows of src / tgt")
+    top = None
+    if tgt_of_problem is not None:
+        top = np.ascontiguousarray(np.asarray(tgt_of_problem, dtype=np.int32))
+        if len(top) != nb:
+            raise _lib.AprHipError("icp_batch: one target segment per problem expected")
+    if not torch.is_tensor(init):
+        init = torch.from_numpy(np.ascontiguousarray(np.asarray(init, dtype=np.float64)))
+    init = init.to(device=src.device, dtype=torch.float64).contiguous()
+    if init.numel() != nb * 16:
+        raise _lib.AprHipError(f"icp_batch: init must hold {nb} 4x4 transforms")
+    lib = _lib_()
+    rec = torch.empty((nb, ICP_RECORD_DOUBLES), dtype=torch.float64, device=src.device)
+    corr = torch.empty(src.shape[0], dtype=torch.int32, device=src.device) if want_corr else None
+    sb = int(lib.apr_icp_scratch_bytes(src.shape[0], tgt.shape[0], nb))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=src.device)
+    check(lib.apr_icp_batch(ptr(src), so.ctypes.data_as(C.c_void_p), ptr(tgt), to.ctypes.data_as(C.c_void_p), n_tgt,
+                            None if top is None else top.ctypes.data_as(C.c_void_p), nb, ptr(init), float(max_dist),
+                            int(max_iteration), float(relative_fitness), float(relative_rmse), ptr(rec), ptr(corr),
+                            ptr(scratch), sb, stream()))
+    return rec, corr

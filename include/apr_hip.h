@@ -1020,6 +1020,38 @@ int apr_circle_backward(const float* a_feats, const float* a_pts, const int32_t*
 int apr_circle_scatter(const float* d_anchor, const int32_t* row, int32_t p, int32_t d, float* d_full, int64_t n_rows,
                        void* stream);
 
+/* ------------------------------------------------------------------------
+ * Point-to-point ICP, the pose refinement in front of the aggregated point cloud:
+ *   o3d.pipelines.registration.registration_icp(next, curr, 0.2, eye(4), TransformationEstimationPointToPoint(),
+ *   ICPConvergenceCriteria(max_iteration=200)) at FCGF_APR/lib/complement_data_loader.py:369-405 (_get_icp,
+ *   _get_neighbourhood_icp), FCGF_APR/lib/data_loaders.py:460-463, Predator_APR/datasets/kitti.py:201-204, 424-428, 558-560.
+ *
+ * nb independent problems in ONE call (the 2k complement frames of a key frame, or a batch of pairs).  Problem i moves the
+ * source rows src_offsets_host[i] .. [i + 1] onto target SEGMENT tgt_of_problem_host[i] (rows tgt_offsets_host[s] .. [s + 1]
+ * of tgt; NULL: segment i, n_tgt == nb), so several problems may share one target.  init f64[nb,16] (row-major 4x4).
+ * nb, n_tgt <= 64.
+ *
+ * open3d >= 0.12 RegistrationICP: evaluate T = init; up to max_iteration times { U = Umeyama (rotation + translation, no
+ * scale) of the corresponded pairs, T = U T, evaluate again, stop when |d fitness| < relative_fitness and |d rmse| <
+ * relative_rmse }.  No correspondences: U is the identity.  max_iteration = 0: the evaluation of init.
+ * Arithmetic: p = fl32(T s) from the ORIGINAL fp32 row and the cumulative fp64 T, ((T0 x + T1 y) + T2 z) + T3 in fp64,
+ * rounded once; d^2 = (dx^2 + dy^2) + dz^2 in fp32, every operation rounded; a correspondence needs d^2 < fl32(max_dist)^2
+ * (fp32 product) STRICTLY; ties go to the smallest target row.  Means, cross-covariance and sum d^2 in fp64, fixed order:
+ * the same bits run to run and for a problem alone or inside a batch.
+ *
+ * result f64[nb, APR_ICP_RECORD_DOUBLES]: T[16], fitness = #corr / #source rows, inlier_rmse = sqrt(sum d^2 / #corr) (0
+ * without correspondences), #corr, iterations run.  corr i32[total source rows] (may be NULL): the target row of every
+ * source row, counted from the start of its target segment, or -1.
+ * The iteration runs on the device: the host enqueues rounds in chunks and reads the per-problem `done` flags once per
+ * chunk, one chunk behind the queue; kernels of a finished problem return at once.  Synchronises `stream` before it
+ * returns. */
+#define APR_ICP_RECORD_DOUBLES 20
+size_t apr_icp_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb);
+int apr_icp_batch(const float* src, const int64_t* src_offsets_host, const float* tgt, const int64_t* tgt_offsets_host,
+                  int32_t n_tgt, const int32_t* tgt_of_problem_host, int32_t nb, const double* init, double max_dist,
+                  int32_t max_iteration, double relative_fitness, double relative_rmse, double* result, int32_t* corr,
+                  void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
