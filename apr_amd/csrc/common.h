@@ -121,7 +121,17 @@ struct AprSearchGrid {
   float cell;
   const int4* cell_coords;   // [n_cells] (cloud, cx, cy, cz) of every occupied cell, by cell id
   const int* n_cells;        // device-side count of occupied cells
+  const int* status;         // device word, valid once the build has run: 0, or why the grid must not be searched --
+                             // 1 / 2 from the cell map (key range, table full), 3 = a cell index >= APR_GRID_MARGIN_CELLS
 };
+// The search grids divide in fp32: a point's cell is floor(fl(fl(p - min) / cell)).  A caller that probes the 3^3 cells
+// around a query for targets within r = cell / 1.01 (icp.hip) relies on the 1 % to cover that rounding.  Both roundings are
+// relative (half an ulp of the extent, half an ulp of the quotient), so the quotient u is off by at most u * 2^-23 and the
+// quotients of a query and of a target within reach differ by at most r / cell + (u_p + u_q) * 2^-23, where
+// r / cell <= 0.9900992 (fl(1.01f), the rounded product, and the fp32 test d^2 < fl(r)^2 taken together).  The floors differ
+// by at most 1 while that is <= 1, i.e. while u_p + u_q <= 0.0099008 * 2^23 = 83053: every cell index below 41526.
+// Rounded down to 5 * 2^13; below the packed key's 2^17, so this is the limit that binds.
+#define APR_GRID_MARGIN_CELLS 40960
 size_t apr_internal_grid_bytes(int64_t n);
 int apr_internal_search_grid(const float* pts, int64_t n, float cell, void* scratch, AprSearchGrid* out,
                              hipStream_t st);

@@ -4,8 +4,9 @@
 //   Predator_APR/datasets/kitti.py:201-204, 424-428, 558-560.
 //
 // One call = one grid build over the target segments (cell = max_dist, widened by 1 %: the cell coordinate is a rounded
-// fp32 quotient, and a target at d < max_dist must never fall outside the 27 cells probed), then per ROUND two launches that
-// cover every problem of the batch:
+// fp32 quotient, and a target at d < max_dist must never fall outside the 27 cells probed -- proven for cell indices below
+// APR_GRID_MARGIN_CELLS, common.h; a segment that extends further is refused with APR_ERANGE), then per ROUND two launches
+// that cover every problem of the batch:
 //   k_icp_assoc : thread per source row.  p = fl32(T * s) (fp64 product of the ORIGINAL row with the cumulative fp64 T,
 //                 rounded once), 27-cell probe, d^2 = (dx^2 + dy^2) + dz^2 in fp32 with every operation rounded, d^2 < r^2
 //                 strictly, ties to the smallest target row.  The moved cloud never reaches memory: each workgroup leaves 17
@@ -48,11 +49,14 @@ __global__ void k_icp_init(const double* __restrict__ init, int nb, double* __re
   if (k == 0) done[b] = 0;
 }
 
-// target rows in bucket order, one 16-B record each: (x, y, z, bits(global row))
-__global__ void k_icp_pack(const float* __restrict__ b, int64_t m, const int* __restrict__ sorted, float4* __restrict__ rows) {
+// target rows in bucket order, one 16-B record each: (x, y, z, bits(global row)).  A grid whose status word is set is not
+// read at all, here or in the rounds: a row outside the key range is in no bucket, so the buckets end at
+// start[n_cells] < m and the tail of `sorted` behind them was never written -- an index from there is anything.  The
+// bound on e keeps that true whatever the status says.
+__global__ void k_icp_pack(const float* __restrict__ b, int64_t m, AprSearchGrid g, float4* __restrict__ rows) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  const int j = sorted[e];
+  if (*g.status != 0 || e >= m || e >= g.start[*g.n_cells]) return;
+  const int j = g.sorted[e];
   rows[e] = make_float4(b[3 * (int64_t)j], b[3 * (int64_t)j + 1], b[3 * (int64_t)j + 2], __int_as_float(j));
 }
 
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_assoc(const float* __restrict
   __shared__ double s_w[4][kIcpSums];
   int prob = 0;
   while (prob + 1 < sg.nb && (int)blockIdx.x >= sg.blk0[prob + 1]) ++prob;
-  if (done[prob]) return;
+  if (done[prob] || *g.status != 0) return;                  // a flagged grid is never searched (k_icp_pack)
   const int seg = sg.tseg[prob];
   const int64_t i = (int64_t)sg.a0[prob] + (int64_t)((int)blockIdx.x - sg.blk0[prob]) * kIcpBlock + threadIdx.x;
   double v[kIcpSums];
@@ -198,12 +202,16 @@ __device__ inline void icp_horn(const double S[3][3], double R[3][3]) {
 }
 
 __global__ __launch_bounds__(kIcpBlock) void k_icp_update(IcpBatch sg, const double* __restrict__ partial, int max_iteration,
-                                                          double rel_fitness, double rel_rmse, double* __restrict__ rec,
-                                                          int* __restrict__ done) {
+                                                          double rel_fitness, double rel_rmse, const int* __restrict__ grid_status,
+                                                          double* __restrict__ rec, int* __restrict__ done) {
   __shared__ double s_w[4][kIcpSums];
   __shared__ double s_tot[kIcpSums];
   const int prob = blockIdx.x;
   if (done[prob]) return;
+  if (*grid_status != 0) {                                     // no association ran: the record stays at init, the host
+    if (threadIdx.x == 0) done[prob] = 1;                      // stops enqueueing and returns APR_ERANGE
+    return;
+  }
   double v[kIcpSums];
 #pragma unroll
   for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
@@ -323,14 +331,16 @@ APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, con
   AprSearchGrid g;
   int rc = apr_internal_search_grid_batch(tgt, m, tlen, n_tgt, rf * 1.01f, w.grid, &g, st);
   if (rc != APR_OK) return rc;
-  hipLaunchKernelGGL(k_icp_pack, dim3((unsigned)cdiv64(m, 256)), dim3(256), 0, st, tgt, m, g.sorted, w.rows);
+  hipLaunchKernelGGL(k_icp_pack, dim3((unsigned)cdiv64(m, 256)), dim3(256), 0, st, tgt, m, g, w.rows);
   hipLaunchKernelGGL(k_icp_init, dim3((unsigned)cdiv64(nb * APR_ICP_RECORD_DOUBLES, 256)), dim3(256), 0, st, init, (int)nb,
                      result, w.done);
   APR_LAUNCH_CHECK();
 
   // rounds 0 .. max_iteration; a look at the flags after every chunk, taken one chunk late so that the queue never drains
-  static thread_local int* flags_host = nullptr;             // pinned, [2][kIcpMaxProblems]
-  if (!flags_host) APR_HIP(hipHostMalloc((void**)&flags_host, 2 * kIcpMaxProblems * sizeof(int), hipHostMallocDefault));
+  static thread_local int* flags_host = nullptr;             // pinned, [2][kIcpMaxProblems], then the grid's status word
+  if (!flags_host)
+    APR_HIP(hipHostMalloc((void**)&flags_host, (2 * kIcpMaxProblems + 1) * sizeof(int), hipHostMallocDefault));
+  int* grid_status = flags_host + 2 * kIcpMaxProblems;
   hipEvent_t ev[2] = {nullptr, nullptr};
   for (int k = 0; k < 2; ++k)
     if (hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) {
@@ -346,10 +356,11 @@ APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, con
       hipLaunchKernelGGL(k_icp_assoc, dim3((unsigned)nblk), dim3(kIcpBlock), 0, st, src, (const float4*)w.rows, g, sg, r2,
                          (const double*)result, (const int*)w.done, w.partial, corr);
       hipLaunchKernelGGL(k_icp_update, dim3((unsigned)nb), dim3(kIcpBlock), 0, st, sg, (const double*)w.partial,
-                         (int)max_iteration, relative_fitness, relative_rmse, result, w.done);
+                         (int)max_iteration, relative_fitness, relative_rmse, g.status, result, w.done);
     }
     APR_LAUNCH_CHECK();
     APR_HIP(hipMemcpyAsync(flags_host + (c & 1) * kIcpMaxProblems, w.done, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (c == 0) APR_HIP(hipMemcpyAsync(grid_status, g.status, sizeof(int), hipMemcpyDeviceToHost, st));
     APR_HIP(hipEventRecord(ev[c & 1], st));
     return APR_OK;
   };
@@ -368,6 +379,17 @@ APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, con
   if (rc == APR_OK && hipStreamSynchronize(st) != hipSuccess) {
     apr_set_error("apr_icp_batch: hipStreamSynchronize failed");
     rc = APR_EHIP;
+  }
+  // a flagged grid: every kernel after the build left at once (k_icp_pack), result holds init and corr was not written
+  if (rc == APR_OK && *grid_status != 0) {
+    if (*grid_status == 3)
+      apr_set_error("apr_icp_batch: a target segment spans more than the cell range of the search grid, %d cells of 1.01 * "
+                    "max_dist per axis (beyond it the 1 %% no longer covers the float32 rounding of the cell coordinate; "
+                    "the packed key itself ends at %d)", APR_GRID_MARGIN_CELLS, APR_AXIS_BIAS);
+    else
+      apr_set_error("apr_icp_batch: search grid build failed, status %d (1: cell index outside the cell range of the "
+                    "packed key, 2: cell table full)", *grid_status);
+    rc = APR_ERANGE;
   }
   (void)hipEventDestroy(ev[0]);
   (void)hipEventDestroy(ev[1]);

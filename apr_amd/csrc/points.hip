@@ -121,14 +121,20 @@ __device__ inline int wave_group_rank(int id, bool active, int* group_size, int*
   return rank;
 }
 
+// A point whose cell leaves the key range belongs to no cell (k_insert has flagged it): packed all the same, its overflow
+// bit would run into the neighbouring field and file the point under another cell's key.  max_cell > 0 (search grids):
+// a cell index >= max_cell sets the status word to 3, whatever k_insert left there.
 __global__ void k_cell_of(const int4* __restrict__ coords, int64_t n, const unsigned long long* __restrict__ keys,
-                          const int* __restrict__ vals, uint32_t mask, int* __restrict__ cell,
-                          int* __restrict__ cnt) {
+                          const int* __restrict__ vals, uint32_t mask, int max_cell, int* __restrict__ cell,
+                          int* __restrict__ cnt, int* __restrict__ status) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int id = -1;
   if (i < n) {
     int4 c = coords[i];
-    id = table_lookup(keys, vals, mask, apr_pack_key(c.x, c.y, c.z, c.w));
+    if (apr_key_in_range(c.x, c.y, c.z, c.w)) id = table_lookup(keys, vals, mask, apr_pack_key(c.x, c.y, c.z, c.w));
+    if (max_cell > 0 && ((unsigned)c.y >= (unsigned)max_cell || (unsigned)c.z >= (unsigned)max_cell ||
+                         (unsigned)c.w >= (unsigned)max_cell))
+      *status = 3;
     cell[i] = id;
   }
   int gsz, lead;
@@ -712,7 +718,8 @@ __global__ void k_set_starts(int* __restrict__ dst, BatchStarts s, int n) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = s.v[threadIdx.x];
 }
 
-// points -> cells -> buckets.  mode as in k_cell_coords.
+// points -> cells -> buckets.  mode as in k_cell_coords.  The search grids (mode 1) also flag cell indices from
+// APR_GRID_MARGIN_CELLS on in w.status; whether that matters is the caller's business (AprSearchGrid::status).
 int build_grid(const float* pts, int64_t n, const int32_t* lengths_host, int nb, float cell, int mode, GridWork& w,
                hipStream_t st) {
   BatchStarts bs;
@@ -732,7 +739,7 @@ int build_grid(const float* pts, int64_t n, const int32_t* lengths_host, int nb,
   APR_HIP(hipMemsetAsync(w.cnt, 0, n * 4, st));
   APR_HIP(hipMemsetAsync(w.cursor, 0, n * 4, st));
   hipLaunchKernelGGL(k_cell_of, dim3(nblk), dim3(kBlock), 0, st, w.coords, n, w.keys, w.vals, (uint32_t)(w.cap - 1),
-                     w.cell, w.cnt);
+                     mode == 1 ? APR_GRID_MARGIN_CELLS : 0, w.cell, w.cnt, w.status);
   // block sums in w.sorted (free until k_fill); n cells at most
   const unsigned nscan = (unsigned)cdiv64(n, kScanBlock);
   hipLaunchKernelGGL(k_scan_sums, dim3(nscan), dim3(256), 0, st, w.cnt, w.n_cells, w.sorted);
@@ -822,6 +829,7 @@ int apr_internal_search_grid(const float* pts, int64_t n, float cell, void* scra
   out->cell = cell;
   out->cell_coords = w.cell_coords;
   out->n_cells = w.n_cells;
+  out->status = w.status;
   return APR_OK;
 }
 
@@ -844,6 +852,7 @@ int apr_internal_search_grid_batch(const float* pts, int64_t n, const int32_t* l
   out->cell = cell;
   out->cell_coords = w.cell_coords;
   out->n_cells = w.n_cells;
+  out->status = w.status;
   return APR_OK;
 }
 

@@ -33,7 +33,7 @@ extern "C" {
 #define APR_EINVAL (-1)   /* bad argument / shape */
 #define APR_EHIP (-2)     /* HIP runtime error */
 #define APR_ETIMEOUT (-3) /* apr_event_wait_timeout: the event was not reached before the deadline */
-#define APR_ERANGE (-3)   /* coordinate outside the packed-key range */
+#define APR_ERANGE (-3)   /* coordinate outside the packed-key range (apr_icp_batch: outside the search grid's cell range) */
 
 const char* apr_last_error(void);
 int apr_version(void);
@@ -1044,7 +1044,14 @@ int apr_circle_scatter(const float* d_anchor, const int32_t* row, int32_t p, int
  * source row, counted from the start of its target segment, or -1.
  * The iteration runs on the device: the host enqueues rounds in chunks and reads the per-problem `done` flags once per
  * chunk, one chunk behind the queue; kernels of a finished problem return at once.  Synchronises `stream` before it
- * returns. */
+ * returns.
+ *
+ * Range: the search grid's cell is fl32(max_dist) * 1.01f, its origin the minimum of each target segment.  A segment may span
+ * at most 40960 cells per axis (extent < 41369 * max_dist: 8.2 km at max_dist = 0.2, 41 m at 1e-3).  Up to that index the
+ * 1 % widening provably covers the float32 rounding of a cell coordinate, so that no target within max_dist is missed; the
+ * packed cell key itself would end at 2^17.  A segment beyond it: APR_ERANGE; no kernel searches such a grid, result holds
+ * init (iterations 0) and corr is not written.  The flag travels with the first copy of the `done` flags and is looked at
+ * after the synchronisation above.  Source rows may lie anywhere: a row too far from its segment has no correspondence. */
 #define APR_ICP_RECORD_DOUBLES 20
 size_t apr_icp_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb);
 int apr_icp_batch(const float* src, const int64_t* src_offsets_host, const float* tgt, const int64_t* tgt_offsets_host,

@@ -166,3 +166,131 @@ def icp_case(trans_m, rot_deg, seed=3):
     tgt = f0[voxel_first_rows(f0, 0.05)]
     src = apply_transform(f1[voxel_first_rows(f1, 0.05)], perturbation(trans_m, rot_deg, seed) @ T1)
     return np.ascontiguousarray(src), np.ascontiguousarray(tgt)
+
+
+# ---- small seeded clouds for the batch-layout tests (tests/test_icp_batch_gpu.py, checked on the CPU in test_icp_cpu.py) ----
+BOX_LO = np.array([-4.0, -2.5, -1.0])      # a 12 x 8 x 3 m box off centre: coordinates of both signs on every axis
+BOX_HI = np.array([8.0, 5.5, 2.0])
+
+
+def box_cloud(m, seed, shift=(0.0, 0.0, 0.0)):
+    """m points spread evenly over the six faces of the box, 1 cm noise, moved by `shift`.  -> float32 [m,3]."""
+    rng = np.random.default_rng(seed)
+    ext = BOX_HI - BOX_LO
+    area = np.array([ext[1] * ext[2], ext[0] * ext[2], ext[0] * ext[1]]).repeat(2)
+    face = rng.choice(6, size=m, p=area / area.sum())
+    p = BOX_LO + rng.uniform(size=(m, 3)) * ext
+    axis, far = face // 2, face % 2 == 1
+    p[np.arange(m), axis] = np.where(far, BOX_HI[axis], BOX_LO[axis])
+    p += rng.normal(0.0, 0.01, size=(m, 3))
+    return np.ascontiguousarray((p + np.asarray(shift, dtype=np.float64)).astype(np.float32))
+
+
+def box_source(tgt, n, i, seed):
+    """n rows of tgt (without repetition) with 5 mm noise, moved by the inverse of perturbation(0.05 + 0.04 i, 0.5 + 0.4 i,
+    seed): ICP from the identity has to find that perturbation.  -> float32 [n,3]."""
+    rng = np.random.default_rng(seed)
+    rows = rng.choice(len(tgt), size=n, replace=False)
+    s = tgt[rows].astype(np.float64) + rng.normal(0.0, 0.005, size=(n, 3))
+    inv = np.linalg.inv(perturbation(0.05 + 0.04 * i, 0.5 + 0.4 * i, seed))
+    return np.ascontiguousarray((s @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32))
+
+
+RAGGED_TGT_ROWS = (3000, 700, 1900)
+RAGGED_TGT_SEEDS = (100, 101, 102)
+RAGGED_SRC_ROWS = (1, 255, 256, 257, 513, 600, 64, 300)
+RAGGED_SRC_SEEDS = (200, 201, 202, 203, 204, 205, 212, 207)
+RAGGED_TGT_OF_PROBLEM = (2, 0, 2, 1, 0, 1, 2, 0)
+
+
+def ragged_batch():
+    """Case (a): three target segments of different sizes, eight sources whose lengths sit on either side of the 256-row
+    workgroup (1, 255, 256, 257, 513, ...), a non-monotone problem -> segment table.
+    -> (targets [3], sources [8], tgt_of_problem [8])."""
+    tgts = [box_cloud(m, s) for m, s in zip(RAGGED_TGT_ROWS, RAGGED_TGT_SEEDS)]
+    srcs = [box_source(tgts[RAGGED_TGT_OF_PROBLEM[i]], n, i, s)
+            for i, (n, s) in enumerate(zip(RAGGED_SRC_ROWS, RAGGED_SRC_SEEDS))]
+    return tgts, srcs, list(RAGGED_TGT_OF_PROBLEM)
+
+
+FULL_SEED = 300
+
+
+def full_batch(nb=64):
+    """Case (c): nb problems on nb segments of their own, every length different (targets 200 .. 400 rows, sources
+    40 .. 300 rows).  The default mapping pairs problem i with segment i.  -> (targets [nb], sources [nb])."""
+    tgts = [box_cloud(200 + (i * 37) % 201, FULL_SEED + i) for i in range(nb)]
+    srcs = [box_source(tgts[i], min(40 + (i * 53) % 261, len(tgts[i])), i % 4, FULL_SEED + 1000 + i) for i in range(nb)]
+    return tgts, srcs
+
+
+CHUNK_TGT_SEED = 400
+CHUNK_FIXED = (600, 5, 205)             # (rows, i, seed) of the fixed-count problem
+CHUNK_BATCH = ((255, 1, 201), (600, 5, 205), (300, 7, 205))    # the oracle stops below 8, in 9 .. 15, at 16 or later
+
+
+def chunk_target():
+    return box_cloud(3000, CHUNK_TGT_SEED)
+
+
+def chunk_sources():
+    """Case (d): -> (the 600-row source of the fixed-count runs, the three sources of the batch that stops in three
+    different chunks of 8 rounds)."""
+    tgt = chunk_target()
+    return box_source(tgt, *CHUNK_FIXED), [box_source(tgt, *c) for c in CHUNK_BATCH]
+
+
+FAR_SHIFT = (1000.0, -2000.0, 50.0)
+FACE_MAX_DIST = 0.2
+
+
+def geometry_cases():
+    """Case (e): name -> (src, tgt, max_dist), all float32.
+    one_cell    max_dist = 50 m on the 12 m box: one grid cell holds every target, every source row has a partner.
+    far         both clouds moved by (1000, -2000, 50) m, where a float32 ulp is 1.2e-4 m.
+    outside     the last 8 source rows lie 5 m outside the target's bounding box: beyond the minimum on one axis each (3),
+                beyond the maximum on one axis each (3), beyond both corners (2).  No partner for any of them.
+    cell_faces  targets ON the faces of the search grid's cells, origin + k * (float32(max_dist) * 1.01f) in float32 as
+                the kernel builds them; sources max_dist / 2 on either side of every face, the outermost ones outside the
+                target's bounding box."""
+    cases = {}
+    tgt = box_cloud(3000, 500)
+    cases["one_cell"] = (box_source(tgt, 600, 2, 501), tgt, 50.0)
+    tgt = box_cloud(2000, 510)
+    src = box_source(tgt, 400, 1, 511)
+    sh = np.asarray(FAR_SHIFT)
+    cases["far"] = ((src.astype(np.float64) + sh).astype(np.float32), (tgt.astype(np.float64) + sh).astype(np.float32), 0.2)
+    tgt = box_cloud(2000, 520)
+    lo, hi = tgt.min(0).astype(np.float64), tgt.max(0).astype(np.float64)
+    mid = (lo + hi) / 2
+    out = []
+    for d in range(3):
+        a, b = mid.copy(), mid.copy()
+        a[d], b[d] = lo[d] - 5.0, hi[d] + 5.0
+        out += [a, b]
+    out = [out[0], out[2], out[4], out[1], out[3], out[5], lo - 5.0, hi + 5.0]
+    cases["outside"] = (np.concatenate([box_source(tgt, 300, 1, 521), np.asarray(out, dtype=np.float32)]), tgt, 0.2)
+    cell = np.float32(FACE_MAX_DIST) * np.float32(1.01)
+    origin = np.array([-3.7, 1.3, 0.2], dtype=np.float32)
+    k = np.stack(np.meshgrid(np.arange(6), np.arange(5), np.arange(4), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    tgt = origin + k * cell                                     # float32 product and sum, each rounded
+    assert tgt.dtype == np.float32
+    half = np.float32(FACE_MAX_DIST / 2)
+    src = np.concatenate([tgt + np.float32(s) * half * np.eye(3, dtype=np.float32)[d] for d in range(3) for s in (-1, 1)])
+    cases["cell_faces"] = (np.ascontiguousarray(src), np.ascontiguousarray(tgt), FACE_MAX_DIST)
+    return cases
+
+
+RANGE_MAX_DIST = 1e-3
+
+
+def range_case(gap_m):
+    """Case (f): two clusters of 200 targets in 1 m cubes, `gap_m` apart along x; the sources are the targets displaced by
+    2e-4 m.  The search grid needs (gap_m + 1) / (1.01 * max_dist) cells along x.  -> (src, tgt) float32."""
+    rng = np.random.default_rng(600)
+    c = rng.uniform(0.0, 1.0, size=(400, 3))
+    c[200:, 0] += gap_m
+    tgt = c.astype(np.float32)
+    d = rng.normal(size=(400, 3))
+    d *= 2e-4 / np.linalg.norm(d, axis=1, keepdims=True)
+    return np.ascontiguousarray((tgt.astype(np.float64) + d).astype(np.float32)), np.ascontiguousarray(tgt)

@@ -22,13 +22,15 @@ def test_scratch_size_grows_with_every_argument(lib):
     assert lib.apr_icp_scratch_bytes(100000, 100000, 64) > base
 
 
-def _call(lib, src_off, tgt_off, nb, max_dist=0.2, max_iteration=5):
+def _call(lib, src_off, tgt_off, nb, max_dist=0.2, max_iteration=5, top=None):
     """apr_icp_batch with dummy (never dereferenced) device pointers: only the argument checks may run."""
     so = np.asarray(src_off, dtype=np.int64)
     to = np.asarray(tgt_off, dtype=np.int64)
+    top = None if top is None else np.asarray(top, dtype=np.int32)
     dummy = C.c_void_p(256)
-    return lib.apr_icp_batch(dummy, so.ctypes.data_as(C.c_void_p), dummy, to.ctypes.data_as(C.c_void_p), len(to) - 1, None,
-                             nb, dummy, max_dist, max_iteration, 1e-6, 1e-6, dummy, None, dummy, 1 << 40, None)
+    return lib.apr_icp_batch(dummy, so.ctypes.data_as(C.c_void_p), dummy, to.ctypes.data_as(C.c_void_p), len(to) - 1,
+                             None if top is None else top.ctypes.data_as(C.c_void_p), nb, dummy, max_dist, max_iteration,
+                             1e-6, 1e-6, dummy, None, dummy, 1 << 40, None)
 
 
 @pytest.mark.parametrize("kind", ["no_problem", "empty_source", "zero_max_dist", "negative_max_dist", "negative_iterations"])
@@ -39,6 +41,23 @@ def test_bad_arguments_are_rejected_before_any_launch(lib, kind):
           "negative_max_dist": lambda: _call(lib, [0, 10], [0, 10], 1, max_dist=-0.2),
           "negative_iterations": lambda: _call(lib, [0, 10], [0, 10], 1, max_iteration=-1)}[kind]()
     assert rc == -1                                             # APR_EINVAL
+    assert b"apr_icp_batch" in lib.apr_last_error()
+
+
+@pytest.mark.parametrize("kind", ["65_problems", "65_segments", "segment_past_the_end", "negative_segment", "empty_segment",
+                                  "empty_source_in_the_middle", "default_mapping_needs_one_segment_each"])
+def test_batch_layout_is_checked_before_any_launch(lib, kind):
+    """The limits of the problem and segment tables.  The device pointers are dummies and this machine has no GPU: -1 can
+    only come from a check on the host that ran before the first HIP call."""
+    ten = lambda k: list(range(0, 10 * k + 1, 10))
+    rc = {"65_problems": lambda: _call(lib, ten(65), [0, 10], 65, top=[0] * 65),
+          "65_segments": lambda: _call(lib, ten(3), ten(65), 3, top=[0, 64, 1]),
+          "segment_past_the_end": lambda: _call(lib, ten(3), ten(2), 3, top=[0, 2, 1]),
+          "negative_segment": lambda: _call(lib, ten(3), ten(2), 3, top=[0, -1, 1]),
+          "empty_segment": lambda: _call(lib, ten(2), [0, 10, 10, 20], 2, top=[0, 2]),
+          "empty_source_in_the_middle": lambda: _call(lib, [0, 10, 10, 20], ten(3), 3),
+          "default_mapping_needs_one_segment_each": lambda: _call(lib, ten(3), ten(2), 3)}[kind]()
+    assert rc == -1
     assert b"apr_icp_batch" in lib.apr_last_error()
 
 
@@ -84,3 +103,50 @@ def test_oracle_variants_stop_after_the_same_number_of_iterations(trans_m, rot_d
     assert 1 < a["iterations"] < 200
     assert a["iterations"] == b["iterations"]
     assert rte < 1e-6 and rre < 1e-4                            # arccos near 1 resolves ~1e-5 deg at best
+
+
+def _variants_agree(src, tgt, max_dist=0.2, max_iteration=60, rel_fitness=1e-6, rel_rmse=1e-6, init=None):
+    """Both arithmetic variants of the restatement on one input: the same iteration count, the same correspondence count,
+    identical partners, poses less than 1e-6 m apart.  Exact equality of the kernel's partners with the float32 variant is
+    asserted on the GPU only for inputs that pass this: the kernel differs from the float32 variant (Horn against SVD,
+    summation order) by far less than the two variants differ from each other.  -> the float32 variant's result."""
+    a = O.icp(src, tgt, init, max_dist, max_iteration, rel_fitness, rel_rmse, fp32_round=True)
+    b = O.icp(src, tgt, init, max_dist, max_iteration, rel_fitness, rel_rmse, fp32_round=False)
+    rte, _ = O.pose_error(a["T"], b["T"])
+    assert a["iterations"] == b["iterations"] and a["n_corr"] == b["n_corr"]
+    assert np.array_equal(a["corr"], b["corr"])
+    assert rte < 1e-6
+    return a
+
+
+def test_ragged_batch_fixture_is_stable_under_rounding():
+    tgts, srcs, top = O.ragged_batch()
+    assert len({len(t) for t in tgts}) == 3 and [len(s) for s in srcs] == [1, 255, 256, 257, 513, 600, 64, 300]
+    assert all(700 <= len(t) <= 3000 for t in tgts) and sorted(set(top)) == [0, 1, 2] and top != sorted(top)
+    for t in tgts:                                               # coordinates of both signs on every axis
+        assert (t.min(0) < 0).all() and (t.max(0) > 0).all()
+    its = [_variants_agree(s, tgts[k])["iterations"] for s, k in zip(srcs, top)]
+    print("iterations:", its)
+    # the host looks at the flags after rounds 8, 16, 24, ...: problems that stop in the first, second and third chunk
+    assert min(its) < 8 and any(9 <= i <= 15 for i in its) and max(its) >= 16 and max(its) < 60
+
+
+def test_full_batch_fixture_is_stable_under_rounding():
+    tgts, srcs = O.full_batch()
+    assert len(tgts) == len(srcs) == 64
+    assert all(200 <= len(t) <= 400 for t in tgts) and all(40 <= len(s) <= 300 for s in srcs)
+    assert len({len(t) for t in tgts}) > 32 and len({len(s) for s in srcs}) > 32
+    assert len({(len(s), len(t)) for s, t in zip(srcs, tgts)}) == 64
+    its = [_variants_agree(s, t)["iterations"] for s, t in zip(srcs, tgts)]
+    assert 1 <= min(its) and max(its) < 60 and len(set(its)) > 1
+
+
+def test_chunk_fixtures_are_stable_under_rounding():
+    tgt = O.chunk_target()
+    fixed, batch = O.chunk_sources()
+    assert len(fixed) == 600
+    for k in (1, 7, 8, 9, 15, 16, 17):
+        assert _variants_agree(fixed, tgt, 0.2, k, 0.0, 0.0)["iterations"] == k
+    its = [_variants_agree(s, tgt, 0.2, 200)["iterations"] for s in batch]
+    print("iterations:", its)
+    assert its[0] < 8 and 9 <= its[1] <= 15 and 16 <= its[2] < 200
