@@ -18,12 +18,25 @@ __global__ void k_transform(const float* __restrict__ pts, int64_t n, const floa
   out[3 * i + 2] = x * T[8] + y * T[9] + z * T[10] + T[11];
 }
 
+// |p|^2 as the crop compares it: (x*x + y*y) + z*z, three products and two sums each rounded to float32.  Contraction is
+// switched off for the helper's body (the __f*_rn intrinsics are plain operators in this toolchain and fuse like any other
+// expression), so that the key's maximum and the rows' norms are the SAME function of a point in both kernels and in every
+// unrolled copy of their loops -- a row bit-equal to the key's farthest point is not < the limit, as in the reference
+// (complement_data_loader.py:620-628: one float32 expression on both sides of the strict <).  The build's assembly has
+// v_mul / v_add (or their packed forms) and no v_fma in k_max_sqnorm and k_crop_flags.
+__device__ inline float sqnorm_rn(float x, float y, float z) {
+#pragma clang fp contract(off)
+  const float xx = x * x, yy = y * y, zz = z * z;
+  const float xy = xx + yy;
+  return xy + zz;
+}
+
 // max over points of |p|^2 (bit pattern of a non-negative float orders like an unsigned int)
 __global__ void k_max_sqnorm(const float* __restrict__ pts, int64_t n, unsigned* __restrict__ out_bits) {
   float m = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    m = fmaxf(m, x * x + y * y + z * z);
+    m = fmaxf(m, sqnorm_rn(x, y, z));
   }
   for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
   if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __float_as_uint(m));
@@ -38,7 +51,7 @@ __global__ void k_crop_flags(const float* __restrict__ pts, int64_t n, const uns
   bool f = false;
   if (i < n) {
     const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    f = (x * x + y * y + z * z) < limit;
+    f = sqnorm_rn(x, y, z) < limit;
     flags[i] = f;
   }
   unsigned long long b = __ballot(f);

@@ -9,6 +9,7 @@ import torch
 from apr_amd import synth
 from apr_amd.fcgf.lib import apg
 from oracle import me_oracle as OME
+from tests import apg_oracle as O
 
 pytestmark = pytest.mark.gpu
 
@@ -32,22 +33,27 @@ def test_apg_aggregation_matches_numpy(dev):
     nghb, sel = apg.aggregate_frames(key, frames, poses, 0.3)
     got = nghb.cpu().numpy()
     assert abs(len(got) - len(ref)) <= 3                      # fp32 rounding at the crop boundary
-    if len(got) == len(ref):
-        assert np.allclose(got, ref, atol=1e-4)
-        assert (np.isin(sel.cpu().numpy(), sel_ref).mean() > 0.999)
+    # row by row, whatever the counts: every row matched to the input row it copies (tests/apg_oracle.py)
+    moved_gpu = torch.cat([apg.apply_transform(f, M) for f, M in zip(frames, poses)], 0).cpu().numpy()
+    src, ref_src = O.check_aggregation(key, frames, poses, moved_gpu, got, ref, atol=1e-4)
+    assert (np.isin(src[sel.cpu().numpy()], ref_src[sel_ref]).mean() > 0.999)
 
 
 def test_get_matching_indices_matches_bruteforce(dev):
     a, b, T = synth.make_pair(2, n_beams=8, n_azimuth=400)
     a, b = a[::2], b[::2]
     pairs = apg.get_matching_indices(a, b, T, 0.45).cpu().numpy()
-    src = (a @ T[:3, :3].T.astype(np.float32) + T[:3, 3].astype(np.float32)).astype(np.float32)
-    d2 = ((src[:, None, :] - b[None]) ** 2).sum(-1)
-    ref = np.argwhere(d2 < 0.45 ** 2)
-    assert abs(len(pairs) - len(ref)) <= 4
-    assert len(set(map(tuple, pairs)) ^ set(map(tuple, ref))) <= 8
+    # k_radius ranks by (d2, index) on d2 = ((dx*dx + dy*dy) + dz*dz) with every operation rounded: numpy float32 restates
+    # it exactly, on the GPU's own transformed source (the search is not judged on the transform's rounding)
+    src = apg.apply_transform(a, T).cpu().numpy()
+    ref = O.radius_pairs_f32(src, b, 0.45)
+    assert len(ref) > 1000 and np.array_equal(pairs, ref)      # the set AND the order: by i, then distance, then j
     p1 = apg.get_matching_indices(a, b, T, 0.45, K=1).cpu().numpy()
     assert len(np.unique(p1[:, 0])) == len(p1)                 # at most one (the nearest) match per source point
+    assert np.array_equal(p1, O.first_pair_per_source(ref))
+    # and the transform it was pinned on is the restatement's, to float32 rounding
+    want, bound = O.transform64(a, T)
+    assert (np.abs(src.astype(np.float64) - want) <= bound).all()
 
 
 def test_chamfer_matches_bruteforce(dev):
