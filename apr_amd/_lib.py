@@ -242,6 +242,11 @@ PROTOTYPES = {
     "apr_circle_scatter": (C.c_int, [_p, _p, _i32, _i32, _p, _i64, _p]),
     "apr_icp_scratch_bytes": (_sz, [_i64, _i64, _i32]),
     "apr_icp_batch": (C.c_int, [_p, _p, _p, _p, _i32, _p, _i32, _p, _f64, _i32, _f64, _f64, _p, _p, _p, _sz, _p]),
+    "apr_mutual_select": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "apr_inlier_ratio": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _f32, _p, _p, _p, _p]),
+    "apr_dense_argmax": (C.c_int, [_p, _i64, _i64, _p, _p, _p]),
+    "apr_ransac_pairs_geometric_scratch_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "apr_ransac_pose_pairs_geometric": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _f64, _i64, _i64, _u64, _p, _sz, _p, _p]),
 }
 
 class KpResnetDesc(C.Structure):

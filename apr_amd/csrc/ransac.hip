@@ -1796,3 +1796,153 @@ APR_API int apr_irls_pose(const float* pts0, const float* pts1, const float* wei
   APR_HIP(hipStreamSynchronize(st));
   return APR_OK;
 }
+
+// ---------------------------------------------------------------------------------
+// Pair-list RANSAC: Predator_APR/lib/benchmark_utils.py:205-210, the mutual=True branch of ransac_pose_estimation --
+// open3d <= 0.11 RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_dist, PointToPoint(false), 4,
+// RANSACConvergenceCriteria(max_iter, max_validation)).  PARITY UNPINNED (open3d is not part of this build); restated
+// from the open3d 0.10 source (Registration.cpp):
+//   result = RegistrationResult()                              // identity, fitness 0, rmse 0
+//   if (ransac_n < 3 || corres.size() < ransac_n || max_dist <= 0) return result
+//   for (it = 0; it < max_iteration && it < max_validation; it++) {
+//     draw ransac_n entries of corres (with replacement)       // here: sample_index(seed, it, slot, n_pairs)
+//     T = ComputeTransformation(source, target, sample)         // kabsch4, fp64; no checker of any kind
+//     this = GetRegistrationResultAndCorrespondences(T source, target, kdtree, max_dist)   // k_score_geometric
+//     if (this.fitness > result.fitness || (this.fitness == result.fitness && this.rmse < result.rmse)) result = this
+//   }
+// The strict comparisons keep the earliest iteration among equals (better(): ... then lower it) and never let a
+// hypothesis without inliers replace the default result (k_init_best_pairs starts the running best at 0 inliers).
+// Only the front is new: k_pack_pair_list gathers the 32-byte records from the (i, j) list, k_fit_pairs is the sampler
+// without checkers -- hypothesis `it` lands in slot `it`, so the list is dense, in iteration order and needs no
+// counter.  Kabsch, the grid NN scoring and the lexicographic best are the functions of the entries above.
+// ---------------------------------------------------------------------------------
+namespace {
+
+__global__ void k_pack_pair_list(const float* __restrict__ xyz0, int64_t n0, const float* __restrict__ xyz1, int64_t n1,
+                                 const int* __restrict__ pairs, int64_t np, float4* __restrict__ rec) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= np) return;
+  int64_t i = pairs[2 * k], j = pairs[2 * k + 1];
+  if (i < 0 || i >= n0 || j < 0 || j >= n1) i = j = 0;
+  rec[2 * k] = make_float4(xyz0[3 * i], xyz0[3 * i + 1], xyz0[3 * i + 2], 0.f);
+  rec[2 * k + 1] = make_float4(xyz1[3 * j], xyz1[3 * j + 1], xyz1[3 * j + 2], 0.f);
+}
+
+__global__ __launch_bounds__(256) void k_fit_pairs(const float4* __restrict__ rec, uint32_t np, uint64_t seed, int n_iter,
+                                                   Hyp* __restrict__ hyps, int* __restrict__ n_valid,
+                                                   int* __restrict__ selected) {
+  const int it = blockIdx.x * blockDim.x + threadIdx.x;
+  if (it == 0) *n_valid = n_iter;
+  if (it >= n_iter) return;
+  double s[4][3], t[4][3], T[12];
+  load_samples(rec, seed, (long long)it, np, s, t);
+  kabsch4(s, t, T);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) hyps[it].T[k] = T[k];
+  hyps[it].it = it;
+  hyps[it].inliers = 0;
+  hyps[it].pad = 0;
+  hyps[it].err2 = 0.0;
+  selected[it] = 1;
+}
+
+// open3d's default RegistrationResult as the running best: identity, no inliers, rmse 0
+__global__ void k_init_best_pairs(Hyp* best, long long* total_valid) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) best->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  best->it = -1;
+  best->inliers = 0;
+  best->pad = 0;
+  best->err2 = 0.0;
+  *total_valid = 0;
+}
+
+constexpr int64_t kPairsMaxIter = 1 << 16;
+
+struct PairsScratch {
+  Hyp* best;
+  long long* total_valid;
+  int* n_valid;
+  Hyp* hyps;
+  float4* rec;
+  int* selected;
+  GeoPart* part;
+  void* grid;
+};
+
+int64_t pairs_iterations(int64_t max_iter, int64_t max_validation) { return max_iter < max_validation ? max_iter : max_validation; }
+
+PairsScratch carve_pairs(void* scratch, int64_t n1, int64_t np, int64_t n_iter) {
+  PairsScratch r;
+  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+  r.best = (Hyp*)p;
+  r.total_valid = (long long*)(p + sizeof(Hyp));
+  r.n_valid = (int*)(p + sizeof(Hyp) + 8);
+  p += 256;
+  r.hyps = (Hyp*)p;
+  p += align256((size_t)n_iter * sizeof(Hyp));
+  r.rec = (float4*)p;
+  p += align256((size_t)np * 32);
+  r.selected = (int*)p;
+  p += align256((size_t)n_iter * 4);
+  r.part = (GeoPart*)p;
+  p += align256((size_t)(n_iter + kGeoGrid) * sizeof(GeoPart));
+  r.grid = (void*)p;
+  return r;
+}
+
+}  // namespace
+
+APR_API size_t apr_ransac_pairs_geometric_scratch_bytes(int64_t n0, int64_t n1, int64_t n_pairs, int64_t max_iter,
+                                                        int64_t max_validation) {
+  const int64_t n_iter = pairs_iterations(max_iter, max_validation);
+  if (n0 <= 0 || n1 <= 0 || n_pairs < 0 || n_iter <= 0 || n_iter > kPairsMaxIter) return 0;
+  const size_t np = (size_t)(n_pairs < 1 ? 1 : n_pairs);
+  return 256 + 256 + align256((size_t)n_iter * sizeof(Hyp)) + align256(np * 32) + align256((size_t)n_iter * 4) +
+         align256((size_t)(n_iter + kGeoGrid) * sizeof(GeoPart)) + apr_internal_grid_bytes(n1) + 256;
+}
+
+APR_API int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int32_t* pairs,
+                                            int64_t n_pairs, double max_dist, int64_t max_iter, int64_t max_validation,
+                                            uint64_t seed, void* scratch, size_t scratch_bytes, double* result_host,
+                                            void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  APR_CHECK_ARG(n0 > 0 && n0 < (1ll << 31) && n1 > 0 && n1 < (1ll << 31), "apr_ransac_pose_pairs_geometric: empty point set");
+  APR_CHECK_ARG(n_pairs >= 0 && n_pairs < (1ll << 31), "apr_ransac_pose_pairs_geometric: bad n_pairs");
+  const int64_t n_iter = pairs_iterations(max_iter, max_validation);
+  APR_CHECK_ARG(n_iter > 0 && n_iter <= kPairsMaxIter && max_dist > 0,
+                "apr_ransac_pose_pairs_geometric: need 0 < min(max_iter, max_validation) <= %lld and max_dist > 0",
+                (long long)kPairsMaxIter);
+  APR_CHECK_ARG(xyz0 && xyz1 && result_host && (pairs || n_pairs == 0), "apr_ransac_pose_pairs_geometric: NULL argument");
+  if (n_pairs < 4) {      // open3d: corres.size() < ransac_n -> RegistrationResult()
+    Hyp hb;
+    for (int k = 0; k < 12; ++k) hb.T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    hb.it = -1; hb.inliers = 0; hb.pad = 0; hb.err2 = 0.0;
+    decode_result(hb, 0, result_host);
+    return APR_OK;
+  }
+  APR_CHECK_ARG(scratch && scratch_bytes >= apr_ransac_pairs_geometric_scratch_bytes(n0, n1, n_pairs, max_iter, max_validation),
+                "apr_ransac_pose_pairs_geometric: scratch too small");
+  const PairsScratch r = carve_pairs(scratch, n1, n_pairs, n_iter);
+  AprSearchGrid g;
+  int rc = apr_internal_search_grid(xyz1, n1, (float)(2.0 * max_dist), r.grid, &g, st);
+  if (rc != APR_OK) return rc;
+  hipLaunchKernelGGL(k_init_best_pairs, dim3(1), dim3(1), 0, st, r.best, r.total_valid);
+  hipLaunchKernelGGL(k_pack_pair_list, dim3((unsigned)cdiv64(n_pairs, 256)), dim3(256), 0, st, xyz0, n0, xyz1, n1,
+                     (const int*)pairs, n_pairs, r.rec);
+  hipLaunchKernelGGL(k_fit_pairs, dim3((unsigned)cdiv64(n_iter, 256)), dim3(256), 0, st, r.rec, (uint32_t)n_pairs, seed,
+                     (int)n_iter, r.hyps, r.n_valid, r.selected);
+  hipLaunchKernelGGL(k_score_geometric, dim3(kGeoGrid), dim3(256), 0, st, xyz0, n0, xyz1, g, max_dist, r.hyps, r.n_valid,
+                     (int)n_iter, r.selected, r.part);
+  hipLaunchKernelGGL(k_score_geometric_finish, dim3((unsigned)cdiv64(n_iter, 256)), dim3(256), 0, st, r.hyps, r.n_valid,
+                     (int)n_iter, n0, r.selected, r.part);
+  hipLaunchKernelGGL(k_select, dim3(1), dim3(1024), 0, st, r.hyps, r.n_valid, (int)n_iter, r.best, r.total_valid);
+  APR_LAUNCH_CHECK();
+  Hyp hb;
+  long long tv = 0;
+  APR_HIP(hipMemcpyAsync(&hb, r.best, sizeof(Hyp), hipMemcpyDeviceToHost, st));
+  APR_HIP(hipMemcpyAsync(&tv, r.total_valid, 8, hipMemcpyDeviceToHost, st));
+  APR_HIP(hipStreamSynchronize(st));
+  decode_result(hb, tv, result_host);
+  return APR_OK;
+}

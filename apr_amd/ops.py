@@ -1669,6 +1669,103 @@ def ransac_pose_geometric(xyz0, xyz1, corr, max_dist, edge_ratio=0.9, max_iter=5
     return r[:16].reshape(4, 4).copy(), info
 
 
+MUTUAL_FEATURE_WIDTH = 32      # apr_gathered_argmax covers d == 32 only (final_feats_dim of the four APR configs)
+
+
+def score_argmax(a, b):
+    """Row and column arg-max of a @ b.T for two FULL clouds of descriptors (never forming the matrix) -> (row_arg i32
+    [n_a], col_arg i32 [n_b]), ties to the lowest index: `gathered_argmax` with identity index lists."""
+    a, b = _dev(a, torch.float32, "score_argmax.a"), _dev(b, torch.float32, "score_argmax.b")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise _lib.AprHipError("score_argmax: need two [n, d] matrices of one width")
+    if a.shape[1] != MUTUAL_FEATURE_WIDTH:
+        raise _lib.AprHipError(f"score_argmax: feature width {a.shape[1]} is not covered (the arg-max kernel is limited to "
+                               f"d = {MUTUAL_FEATURE_WIDTH})")
+    if a.shape[0] == 0 or b.shape[0] == 0:
+        raise _lib.AprHipError("score_argmax: empty cloud")
+    dev = a.device
+    ia = torch.arange(a.shape[0], dtype=torch.int32, device=dev)
+    ib = torch.arange(b.shape[0], dtype=torch.int32, device=dev)
+    n = torch.tensor([a.shape[0], b.shape[0]], dtype=torch.int32, device=dev)
+    return gathered_argmax(a, ia, n[0:1], b, ib, n[1:2])
+
+
+def dense_argmax(scores):
+    """np.argmax(scores, 1), np.argmax(scores, 0) of a dense f32 [n, m] GPU matrix -> (row_arg, col_arg) i32, ties to the
+    lowest index."""
+    scores = _dev(scores, torch.float32, "dense_argmax.scores")
+    if scores.dim() != 2 or scores.shape[0] == 0 or scores.shape[1] == 0:
+        raise _lib.AprHipError("dense_argmax: need a non-empty [n, m] matrix")
+    n, m = scores.shape
+    row_arg = torch.empty(n, dtype=torch.int32, device=scores.device)
+    col_arg = torch.empty(m, dtype=torch.int32, device=scores.device)
+    check(_lib_().apr_dense_argmax(ptr(scores), n, m, ptr(row_arg), ptr(col_arg), stream()))
+    return row_arg, col_arg
+
+
+def mutual_select(row_arg, col_arg, n_src_dev=None, n_tgt_dev=None):
+    """The pairs (i, row_arg[i]) with col_arg[row_arg[i]] == i, ascending i -> (pairs i32 [min(n_src, n_tgt), 2], count
+    i32 [1]), both on the device; only the first `count` rows of `pairs` are meaningful.  n_src_dev / n_tgt_dev: device
+    i32 lengths that shorten the two vectors (the lists of `gathered_argmax`)."""
+    row_arg, col_arg = _dev(row_arg, torch.int32, "mutual_select.row_arg"), _dev(col_arg, torch.int32, "mutual_select.col_arg")
+    if row_arg.dim() != 1 or col_arg.dim() != 1 or row_arg.shape[0] == 0 or col_arg.shape[0] == 0:
+        raise _lib.AprHipError("mutual_select: need two non-empty vectors")
+    for name, t in (("n_src_dev", n_src_dev), ("n_tgt_dev", n_tgt_dev)):
+        if t is not None:
+            _dev(t, torch.int32, "mutual_select." + name)
+    n_src, n_tgt = row_arg.shape[0], col_arg.shape[0]
+    pairs = torch.zeros((min(n_src, n_tgt), 2), dtype=torch.int32, device=row_arg.device)
+    count = torch.zeros(1, dtype=torch.int32, device=row_arg.device)
+    check(_lib_().apr_mutual_select(ptr(row_arg), ptr(n_src_dev), n_src, ptr(col_arg), ptr(n_tgt_dev), n_tgt, ptr(pairs),
+                                    ptr(count), stream()))
+    return pairs, count
+
+
+def inlier_ratio(src_pcd, tgt_pcd, rot, trans, row_arg, pairs, count, threshold):
+    """get_inlier_ratio's two legs in one launch -> (dist_wo f32 [n_src], dist_w f32 [len(pairs)], out f32 [8]) on the
+    device; out = ratio_wo, ratio_w, #inliers wo, #inliers w, n_src, #pairs, 0, 0.  Only the first `count` entries of
+    dist_w are meaningful."""
+    src_pcd, tgt_pcd = _dev(src_pcd, torch.float32, "inlier_ratio.src_pcd"), _dev(tgt_pcd, torch.float32, "inlier_ratio.tgt_pcd")
+    rot, trans = _dev(rot, torch.float32, "inlier_ratio.rot"), _dev(trans, torch.float32, "inlier_ratio.trans")
+    row_arg, pairs = _dev(row_arg, torch.int32, "inlier_ratio.row_arg"), _dev(pairs, torch.int32, "inlier_ratio.pairs")
+    count = _dev(count, torch.int32, "inlier_ratio.count")
+    if src_pcd.dim() != 2 or src_pcd.shape[1] != 3 or tgt_pcd.dim() != 2 or tgt_pcd.shape[1] != 3:
+        raise _lib.AprHipError("inlier_ratio: the clouds must be [n, 3]")
+    if rot.numel() != 9 or trans.numel() != 3 or row_arg.shape[0] != src_pcd.shape[0] or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise _lib.AprHipError("inlier_ratio: need rot [3,3], trans [3,1], one row_arg per source point and pairs [k, 2]")
+    n_src, n_tgt, cap = src_pcd.shape[0], tgt_pcd.shape[0], pairs.shape[0]
+    dev = src_pcd.device
+    dist_wo = torch.empty(n_src, dtype=torch.float32, device=dev)
+    dist_w = torch.zeros(cap, dtype=torch.float32, device=dev)
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    check(_lib_().apr_inlier_ratio(ptr(src_pcd), n_src, ptr(tgt_pcd), n_tgt, ptr(rot), ptr(trans), ptr(row_arg), ptr(pairs),
+                                   ptr(count), cap, float(threshold), ptr(dist_wo), ptr(dist_w), ptr(out), stream()))
+    return dist_wo, dist_w, out
+
+
+def ransac_pose_pairs_geometric(xyz0, xyz1, pairs, n_pairs, max_dist, max_iter=50000, max_validation=1000, seed=0):
+    """open3d <= 0.11 registration_ransac_based_on_correspondence (Predator_APR's mutual branch): 4-pair samples of the
+    first `n_pairs` (a host int) rows of `pairs` i32 [k, 2], no checkers, geometric inlier count -> (T [4,4] float64, info)."""
+    xyz0 = _f32(xyz0, "ransac_pairs.xyz0").contiguous()
+    xyz1 = _f32(xyz1, "ransac_pairs.xyz1").contiguous()
+    pairs = _dev(pairs, torch.int32, "ransac_pairs.pairs")
+    n_pairs = int(n_pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 0 <= n_pairs <= pairs.shape[0]:
+        raise _lib.AprHipError("ransac_pose_pairs_geometric: pairs must be int32 [k, 2] with 0 <= n_pairs <= k")
+    n0, n1 = xyz0.shape[0], xyz1.shape[0]
+    lib = _lib_()
+    sb = int(lib.apr_ransac_pairs_geometric_scratch_bytes(n0, n1, n_pairs, int(max_iter), int(max_validation)))
+    scratch = torch.empty(max(sb, 256), dtype=torch.uint8, device=xyz0.device)
+    res = (C.c_double * 20)()
+    check(lib.apr_ransac_pose_pairs_geometric(ptr(xyz0), n0, ptr(xyz1), n1, ptr(pairs), n_pairs, float(max_dist),
+                                              int(max_iter), int(max_validation), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              ptr(scratch), sb, res, stream()))
+    r = np.array(list(res), dtype=np.float64)
+    info = dict(inliers=int(r[16]), rmse=float(r[17]), best_iteration=int(r[18]), n_valid=int(r[19]),
+                fitness=float(r[16]) / max(n0, 1), n_pairs=n_pairs)
+    return r[:16].reshape(4, 4).copy(), info
+
+
 def ransac_pose_geometric_async(xyz0, xyz1, corr, max_dist, edge_ratio=0.9, max_iter=50000, max_validation=1000, seed=0):
     """`ransac_pose_geometric` enqueued without a host synchronisation -> uint8 device tensor holding the raw result;
     fetch the raw results of a batch with one copy and decode each with `ransac_decode`."""

@@ -7,6 +7,13 @@ RANSACConvergenceCriteria(50000, 1000): feature-NN correspondences, 4-point samp
 checkers, Kabsch, and a GEOMETRIC validation of the first 1000 surviving hypotheses.  `get_angle_deviation`
 follows :170-185.  open3d is absent here: parity unpinned, checked against the CPU oracle on the same
 hypothesis stream and against ground truth.
+
+`mutual=True` (:193-211) is open3d 0.10's `registration_ransac_based_on_correspondence` on the mutual nearest-neighbour
+pairs; `get_inlier_ratio` (:227-268) and `mutual_selection` (:271-295) keep the reference's signatures and return shapes.
+The reference forms the n_src x n_tgt score matrix, copies it to the host and allocates three more arrays of that size;
+here `mutual_pairs` gets the same pair list from the two arg-max vectors of the device kernel, and no n x m array exists
+(except in `mutual_selection`, whose caller hands one in and whose result is one by definition).  Descriptors must be
+32 wide (`ops.MUTUAL_FEATURE_WIDTH`).
 """
 import numpy as np
 import torch
@@ -20,16 +27,81 @@ def _dev(t):
     return t.to(device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.float32).contiguous()
 
 
+def _gpu(t):
+    """`_dev` for the mutual-matching entries: the library is loaded first, and without a GPU the refusal is the library
+    layer's own error, as for every op handed CPU tensors (there is no CPU fallback)."""
+    ops._lib_()
+    if not torch.cuda.is_available():
+        raise ops._lib.AprHipError("mutual matching runs on the HIP kernels only: no GPU is visible and there is no CPU fallback")
+    return _dev(t)
+
+
 def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_threshold=0.05, ransac_n=3,
                            max_iteration=50000, max_validation=1000, seed=0, return_info=False):
     if mutual:
-        raise NotImplementedError("mutual selection is not used by the APR tester (lib/tester.py:97)")
+        # :193-211; ransac_n is ignored on this branch, as in the reference, which hard-codes 4 there
+        x0, x1 = _gpu(src_pcd), _gpu(tgt_pcd)
+        row_arg, col_arg = ops.score_argmax(_gpu(src_feat), _gpu(tgt_feat))
+        pairs, count = ops.mutual_select(row_arg, col_arg)
+        n_pairs = int(count.item())                 # the one 4-byte fetch that sizes the call
+        T, info = ops.ransac_pose_pairs_geometric(x0, x1, pairs, n_pairs, distance_threshold, max_iteration,
+                                                  max_validation, seed)
+        sel = pairs[:n_pairs].cpu().numpy().astype(np.int64)
+        row_sel, col_sel = np.ascontiguousarray(sel[:, 0]), np.ascontiguousarray(sel[:, 1])
+        return (T, row_sel, col_sel, info) if return_info else (T, row_sel, col_sel)
     if ransac_n != 4:
         raise NotImplementedError("the HIP RANSAC kernel is specialised for ransac_n = 4 (KITTI / nuScenes)")
     x0, x1 = _dev(src_pcd), _dev(tgt_pcd)
     corr = ops.feature_nn(_dev(src_feat), _dev(tgt_feat))
     T, info = ops.ransac_pose_geometric(x0, x1, corr, distance_threshold, 0.9, max_iteration, max_validation, seed)
     return (T, info) if return_info else T
+
+
+def mutual_pairs(src_feat, tgt_feat):
+    """(row_sel, col_sel) int64: `np.where(mutual_selection(src_feat @ tgt_feat.T))` without the matrix -- the entries that
+    are the maximum of both their row and their column, ascending row, ties to the lowest index as np.argmax."""
+    row_arg, col_arg = ops.score_argmax(_gpu(src_feat), _gpu(tgt_feat))
+    pairs, count = ops.mutual_select(row_arg, col_arg)
+    sel = pairs[:int(count.item())].cpu().numpy().astype(np.int64)
+    return np.ascontiguousarray(sel[:, 0]), np.ascontiguousarray(sel[:, 1])
+
+
+def mutual_selection(score_mat):
+    """Boolean [B, N, M] mask, True where an entry is the maximum along both its row and its column (:271-295).  The
+    compatibility form for a caller that already holds the score matrix ([B, N, M] or [N, M], array or tensor): the arg-maxes
+    run on the device, the mask is filled on the host.  `mutual_pairs` is the matrix-free form."""
+    if isinstance(score_mat, np.ndarray):
+        score_mat = torch.from_numpy(np.ascontiguousarray(score_mat))
+    if score_mat.dim() == 2:
+        score_mat = score_mat[None]
+    B, n, m = score_mat.shape
+    mutuals = np.zeros((B, n, m), dtype=bool)
+    for b in range(B):
+        row_arg, col_arg = ops.dense_argmax(_gpu(score_mat[b]))
+        pairs, count = ops.mutual_select(row_arg, col_arg)
+        sel = pairs[:int(count.item())].cpu().numpy()
+        mutuals[b, sel[:, 0], sel[:, 1]] = True
+    return mutuals
+
+
+def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_distance_threshold=0.1):
+    """Inlier ratios with ('w') and without ('wo') the mutual check (:227-268) -> the reference's nested dict:
+    results[leg]['distance'] float32 array, results[leg]['inlier_ratio'] 0-dim float32 CPU tensor."""
+    x0, x1 = _gpu(src_pcd), _gpu(tgt_pcd)
+    row_arg, col_arg = ops.score_argmax(_gpu(src_feat), _gpu(tgt_feat))
+    pairs, count = ops.mutual_select(row_arg, col_arg)
+    dist_wo, dist_w, out = ops.inlier_ratio(x0, x1, _gpu(rot).reshape(3, 3), _gpu(trans).reshape(3, 1), row_arg, pairs, count,
+                                            inlier_distance_threshold)
+    out = out.cpu()                                  # synchronises: ratios, counts and the list length in one fetch
+    n_pairs = int(out[5])
+    results = dict()
+    results['w'] = dict()
+    results['wo'] = dict()
+    results['wo']['distance'] = dist_wo.cpu().numpy()
+    results['wo']['inlier_ratio'] = out[0].clone()
+    results['w']['distance'] = dist_w[:n_pairs].cpu().numpy()
+    results['w']['inlier_ratio'] = out[1].clone()
+    return results
 
 
 def get_correspondences(src_pcd, tgt_pcd, trans, search_voxel_size, K=None):

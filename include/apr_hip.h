@@ -1059,6 +1059,53 @@ int apr_icp_batch(const float* src, const int64_t* src_offsets_host, const float
                   int32_t max_iteration, double relative_fitness, double relative_rmse, double* result, int32_t* corr,
                   void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mutual nearest-neighbour matching, inlier ratios and the pair-list RANSAC of the Predator tester
+ * (Predator_APR/lib/benchmark_utils.py:187-211, :227-268, :271-295).  No n_src x n_tgt array exists on this path.
+ * ------------------------------------------------------------------------ */
+
+/* benchmark_utils.py:271-295 (mutual_selection) + np.where (:201, :261) on the arg-max vectors apr_gathered_argmax writes:
+ * pairs i32[min(n_src_max, n_tgt_max), 2] (row-major) = (i, row_arg[i]) for every i with col_arg[row_arg[i]] == i, in
+ * ascending i; *count i32 on the device = their number.  Entries of `pairs` past *count are not written.  *n_src_dev /
+ * *n_tgt_dev: device-side lengths of row_arg / col_arg (clamped to n_src_max / n_tgt_max; NULL: the max).  Ties were
+ * settled by the arg-max (lowest index, as np.argmax); a row_arg outside [0, n_tgt) is no pair.  Positions come from
+ * ballot + popcount + a block scan: the same bits run to run. */
+int apr_mutual_select(const int32_t* row_arg, const int32_t* n_src_dev, int64_t n_src_max, const int32_t* col_arg,
+                      const int32_t* n_tgt_dev, int64_t n_tgt_max, int32_t* pairs, int32_t* count, void* stream);
+
+/* benchmark_utils.py:246-266 (get_inlier_ratio) in one launch.  src_pcd f32[n_src,3], tgt_pcd f32[n_tgt,3], rot9 f32[9]
+ * (row-major 3x3), trans3 f32[3], row_arg i32[n_src] (the arg-max along each score row), pairs i32[pairs_cap,2] and *count
+ * (device) as apr_mutual_select leaves them.  q = rot p + trans and |q - t| in float32, every operation rounded, sums left
+ * to right.  dist_wo f32[n_src]: distance of every source point to tgt[row_arg]; dist_w f32[pairs_cap]: the same over the
+ * first *count pairs (the rest is not written).  out8 f32[8] = ratio_wo = #(dist_wo < threshold) / n_src, ratio_w =
+ * #(dist_w < threshold) / *count (NaN for an empty list: the mean of nothing), the two integer counts, n_src, *count, 0, 0.
+ * The counts are integer sums; n_src < 2^24 so that they are exact as float32.  An index outside its cloud gives +inf. */
+int apr_inlier_ratio(const float* src_pcd, int64_t n_src, const float* tgt_pcd, int64_t n_tgt, const float* rot9,
+                     const float* trans3, const int32_t* row_arg, const int32_t* pairs, const int32_t* count,
+                     int64_t pairs_cap, float threshold, float* dist_wo, float* dist_w, float* out8, void* stream);
+
+/* np.argmax(scores, 1) / np.argmax(scores, 0) of a dense row-major f32[n,m] matrix the caller already holds (the
+ * compatibility form of mutual_selection): row_arg i32[n], col_arg i32[m], ties to the lowest index.  NaN never wins. */
+int apr_dense_argmax(const float* scores, int64_t n, int64_t m, int32_t* row_arg, int32_t* col_arg, void* stream);
+
+/* benchmark_utils.py:205-210: open3d <= 0.11 RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_dist,
+ * TransformationEstimationPointToPoint(false), ransac_n = 4, RANSACConvergenceCriteria(max_iter, max_validation)).
+ * PARITY UNPINNED (open3d is not part of this build): restated from the open3d 0.10 source --
+ *   for it < min(max_iter, max_validation): draw 4 entries of the pair list (here the counter RNG (seed, it, slot) of the
+ *   other RANSAC entries, index = high word of rng * n_pairs); T = Kabsch without scale (fp64); NO edge-length or distance
+ *   checker; score T geometrically over the WHOLE source cloud: an inlier is a transformed source point whose nearest
+ *   target point lies within max_dist (fp32 d^2 < fl32(max_dist^2), as apr_ransac_pose_geometric).
+ * The best hypothesis: more inliers (fitness), then lower rmse, then lower it.  A hypothesis without inliers never
+ * replaces the default result; n_pairs < 4 returns it at once: identity, fitness 0, best_iteration -1.
+ * pairs i32[n_pairs,2] on the device, rows (source index, target index); n_pairs is a HOST value (one 4-byte fetch of
+ * apr_mutual_select's count).  A pair outside its cloud is read as (0, 0).  result_host f64[20] as apr_ransac_pose
+ * (T[16], inliers, rmse, best iteration, hypotheses scored).  Synchronises `stream`. */
+size_t apr_ransac_pairs_geometric_scratch_bytes(int64_t n0, int64_t n1, int64_t n_pairs, int64_t max_iter,
+                                                int64_t max_validation);
+int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int32_t* pairs,
+                                    int64_t n_pairs, double max_dist, int64_t max_iter, int64_t max_validation, uint64_t seed,
+                                    void* scratch, size_t scratch_bytes, double* result_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
