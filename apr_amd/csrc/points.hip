@@ -11,10 +11,11 @@
 //     in fp32 in that order, so the barycentres are BIT-IDENTICAL to the reference's sequential
 //     `point += p` accumulation (row order differs: libstdc++ unordered_map iteration order is
 //     not reproduced, parity is per cell);
-//   * radius search: one wave per query probes the 27 surrounding cells (cell edge = radius),
-//     lanes stride over the candidates, hits are ballot-compacted into LDS and rank-sorted by
-//     (d2, index); d2 = ((dx*dx) + dy*dy) + dz*dz in fp32 without contraction, `d2 < r*r`
-//     strictly -- nanoflann's L2_Simple_Adaptor / RadiusResultSet arithmetic.
+//   * radius search: one wave per query probes the 27 surrounding cells (cell edge = 1.01 * radius: the
+//     1 % absorbs the two roundings of the fp32 cell index, common.h), lanes stride over the
+//     candidates, hits are ballot-compacted into LDS and rank-sorted by (d2, index);
+//     d2 = ((dx*dx) + dy*dy) + dz*dz in fp32 without contraction (d2_rn), `d2 < r*r` strictly --
+//     nanoflann's L2_Simple_Adaptor / RadiusResultSet arithmetic.
 // All of it is integer / latency-bound work on a few 10^4 points: HBM traffic is negligible, the
 // point is to keep the index build on the device, stream-ordered in front of the encoder.
 #include "common.h"
@@ -61,6 +62,30 @@ __global__ __launch_bounds__(kMinThreads) void k_cloud_min(const float* __restri
   }
 }
 
+// The __f*_rn intrinsics are plain operators in this toolchain and fuse like any other expression:
+// the statements that must keep every rounding of the reference's arithmetic switch contraction off for their body.
+//   d2_rn      : ((dx*dx) + dy*dy) + dz*dz, three differences, three products, two sums (nanoflann's L2_Simple_Adaptor)
+//   cell_index : floor((p - origin) / cell); inlined next to origin = floor(..) * dl the difference would become an FMA
+//   sub_origin : floor(min * (1 / dl)) * dl   (grid_subsampling.cpp:60-89)
+__device__ inline float d2_rn(float qx, float qy, float qz, float px, float py, float pz) {
+#pragma clang fp contract(off)
+  const float dx = qx - px, dy = qy - py, dz = qz - pz;
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  const float xy = xx + yy;
+  return xy + zz;
+}
+__device__ inline int cell_index(float p, float origin, float cell) {
+#pragma clang fp contract(off)
+  const float e = p - origin;
+  return (int)floorf(__fdiv_rn(e, cell));
+}
+__device__ inline float sub_origin(float mn, float dl) {
+#pragma clang fp contract(off)
+  const float inv = __fdiv_rn(1.0f, dl);
+  const float u = mn * inv;
+  return floorf(u) * dl;
+}
+
 __device__ inline int batch_of(const int* __restrict__ starts, int nb, int i) {
   int b = 0;
   while (b + 1 < nb && i >= starts[b + 1]) ++b;
@@ -79,8 +104,8 @@ __global__ void k_cell_coords(const float* __restrict__ pts, int64_t n, const in
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     float o = mins[3 * b + d];
-    if (mode == 0) o = __fmul_rn(floorf(__fmul_rn(o, __fdiv_rn(1.0f, dl))), dl);
-    c[d] = (int)floorf(__fdiv_rn(__fsub_rn(pts[3 * i + d], o), dl));
+    if (mode == 0) o = sub_origin(o, dl);
+    c[d] = cell_index(pts[3 * i + d], o, dl);
   }
   coords[i] = make_int4(b, c[0], c[1], c[2]);
 }
@@ -439,9 +464,9 @@ __global__ __launch_bounds__(256) void k_radius(const float* __restrict__ q, int
   if (qi >= nq) return;
   const int b = batch_of(qstarts, nb, (int)qi);
   const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
-  const int cx = (int)floorf(__fdiv_rn(__fsub_rn(qx, g.mins[3 * b]), g.cell));
-  const int cy = (int)floorf(__fdiv_rn(__fsub_rn(qy, g.mins[3 * b + 1]), g.cell));
-  const int cz = (int)floorf(__fdiv_rn(__fsub_rn(qz, g.mins[3 * b + 2]), g.cell));
+  const int cx = cell_index(qx, g.mins[3 * b], g.cell);
+  const int cy = cell_index(qy, g.mins[3 * b + 1], g.cell);
+  const int cz = cell_index(qz, g.mins[3 * b + 2], g.cell);
   // lanes 0..26 each probe one neighbouring cell; the 27 (start, inclusive-count) pairs go to LDS
   int c_lo = 0, c_n = 0;
   if (lane < 27) {
@@ -499,8 +524,7 @@ __global__ __launch_bounds__(256) void k_radius(const float* __restrict__ q, int
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (base + u * 64 >= total) break;               // wave-uniform
-      const float dx = __fsub_rn(qx, px[u]), dy = __fsub_rn(qy, py[u]), dz = __fsub_rn(qz, pz[u]);
-      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      const float d2 = d2_rn(qx, qy, qz, px[u], py[u], pz[u]);
       const bool hit = sidx[u] >= 0 && d2 < r2;
       const unsigned long long m = __ballot(hit);
       if (MODE >= 1 && hit) {
@@ -541,9 +565,7 @@ __global__ __launch_bounds__(256) void k_radius(const float* __restrict__ q, int
               if (L + step <= 26 && s_incl[wave][L + step - 1] <= t) L += step;
             const int before = L ? s_incl[wave][L - 1] : 0;
             sidx = g.sorted[s_lo[wave][L] + (t - before)];
-            const float dx = __fsub_rn(qx, s[3 * (int64_t)sidx]), dy = __fsub_rn(qy, s[3 * (int64_t)sidx + 1]),
-                        dz = __fsub_rn(qz, s[3 * (int64_t)sidx + 2]);
-            d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            d2 = d2_rn(qx, qy, qz, s[3 * (int64_t)sidx], s[3 * (int64_t)sidx + 1], s[3 * (int64_t)sidx + 2]);
             hit = d2 < r2;
           }
           f(hit, d2, sidx);
@@ -595,7 +617,16 @@ __global__ __launch_bounds__(256) void k_radius(const float* __restrict__ q, int
   for (int e = nhit + lane; e < width; e += 64) out[qi * ld + e] = pad_value;
 }
 
-__global__ void k_max_int(const int* __restrict__ v, int64_t n, int* __restrict__ out) {
+// out = max over v.  build_status != nullptr (the synchronisation-free tables): the launch's first thread also lets the
+// grid's build status (1 / 2 from the cell map, 3 = a cell index >= APR_GRID_MARGIN_CELLS) join the overflow flag,
+// flag = 16 + status, whatever k_radius left there -- a grid that must not be searched outranks a row that could not be
+// ranked.  k_radius has finished when this kernel starts (same stream), and nothing else of this launch touches flag.
+__global__ void k_max_int(const int* __restrict__ v, int64_t n, int* __restrict__ out,
+                          const int* __restrict__ build_status, int* __restrict__ flag) {
+  if (build_status != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int s = *build_status;
+    if (s != 0) *flag = 16 + s;
+  }
   int m = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     m = max(m, v[i]);
@@ -875,37 +906,45 @@ APR_API int apr_radius_neighbors(const float* queries, int64_t nq, const float* 
   int* qstarts = (int*)p;
   p += align256((kMaxBatch + 1) * 4);
   int* maxc = (int*)p;
-  int rc = build_grid(supports, ns, s_lengths_host, nb, radius, 1, w, st);
+  const float cell = 1.01f * radius;   // as icp.hip: the 1 % covers the cell index's fp32 roundings (common.h)
+  int rc = build_grid(supports, ns, s_lengths_host, nb, cell, 1, w, st);
   if (rc != APR_OK) return rc;
   int qs[kMaxBatch + 1];
   qs[0] = 0;
   for (int b = 0; b < nb; ++b) qs[b + 1] = qs[b] + q_lengths_host[b];
   APR_CHECK_ARG(qs[nb] == nq, "apr_radius_neighbors: query batch lengths sum to %d, expected %lld", qs[nb], (long long)nq);
   APR_HIP(hipMemcpyAsync(qstarts, qs, (nb + 1) * 4, hipMemcpyHostToDevice, st));
-  Grid g{w.keys, w.vals, (uint32_t)(w.cap - 1), w.start, w.sorted, w.mins, radius};
+  Grid g{w.keys, w.vals, (uint32_t)(w.cap - 1), w.start, w.sorted, w.mins, cell};
   const float r2 = radius * radius;
   const unsigned grid = (unsigned)cdiv64(nq, 4);
   // counting pass: the reference pads every row to the global maximum neighbour count and the
   // caller then keeps the first `limit` columns, so width = min(max_count, limit)
-  int width = 0;
+  int width = 0, status = 0;
   APR_HIP(hipMemsetAsync(maxc, 0, 4, st));
   hipLaunchKernelGGL(k_radius<0>, dim3(grid), dim3(256), 0, st, queries, nq, qstarts, supports, nb, g, r2, counts,
                      (int*)nullptr, 0, (int64_t)0, 0, w.status);
-  hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, st, counts, nq, maxc);
+  hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, st, counts, nq, maxc, (const int*)nullptr, (int*)nullptr);
   APR_HIP(hipMemcpyAsync(&width, maxc, 4, hipMemcpyDeviceToHost, st));
+  APR_HIP(hipMemcpyAsync(&status, w.status, 4, hipMemcpyDeviceToHost, st));   // the BUILD's word: the counting pass writes none
   APR_HIP(hipStreamSynchronize(st));
+  if (status != 0) {   // supports outside the grid belong to no cell: no table, not a table without them
+    if (status == 3)
+      apr_set_error("apr_radius_neighbors: the supports of a cloud span %d or more cells of 1.01 * radius",
+                    APR_GRID_MARGIN_CELLS);
+    else
+      apr_set_error("apr_radius_neighbors: the search grid could not be built (cell map status %d)", status);
+    return APR_ERANGE;
+  }
   if (limit > 0 && width > limit) width = limit;
   *width_host = width;
   if (out == nullptr) return APR_OK;  // size query only
   APR_CHECK_ARG(width <= out_ld, "apr_radius_neighbors: need %d columns, buffer rows hold %lld", width,
                 (long long)out_ld);
   if (width == 0) return APR_OK;
-  APR_HIP(hipMemsetAsync(w.status, 0, 4, st));
   hipLaunchKernelGGL(k_radius<1>, dim3(grid), dim3(256), 0, st, queries, nq, qstarts, supports, nb, g, r2, counts, out,
                      width, out_ld, (int)ns, w.status);
   APR_LAUNCH_CHECK();
-  int status = 0;
-  APR_HIP(hipMemcpyAsync(&status, w.status, 4, hipMemcpyDeviceToHost, st));
+  APR_HIP(hipMemcpyAsync(&status, w.status, 4, hipMemcpyDeviceToHost, st));   // 0 after the build (checked above)
   APR_HIP(hipStreamSynchronize(st));
   if (status != 0) {
     apr_set_error("apr_radius_neighbors: a query has more than %d neighbours within the radius", kHitCap);
@@ -916,7 +955,8 @@ APR_API int apr_radius_neighbors(const float* queries, int64_t nq, const float* 
 
 // Host-synchronisation-free variant for callers that know the column limit (KPConv's calibrated neighbourhood limits):
 // one fill pass writes limit columns per query (sorted by distance, padded with ns) AND the query's full neighbour
-// count; flags_dev[0] = max count over all queries, flags_dev[1] != 0 if a query overflowed the candidate buffer.
+// count; flags_dev[0] = max count over all queries, flags_dev[1] = 1 if a query overflowed the candidate buffer, 16 + the
+// grid's build status if that is not 0 (17 / 18: cell map, 19: a cell index >= APR_GRID_MARGIN_CELLS): no table then.
 // The reference's width is min(max count, limit): a caller that needs it reads flags_dev when convenient (one
 // synchronisation for a whole pyramid of tables) and drops the all-padding columns [max count, limit) if any.
 static int radius_async(const float* queries, int64_t nq, const float* supports, int64_t ns,
@@ -934,8 +974,9 @@ static int radius_async(const float* queries, int64_t nq, const float* supports,
   int* counts = (int*)p;
   p += align256(nq * 4);
   int* qstarts = (int*)p;
+  const float cell = 1.01f * radius;   // as apr_radius_neighbors
   if (!reuse_grid) {
-    int rc = build_grid(supports, ns, s_lengths_host, nb, radius, 1, w, st);
+    int rc = build_grid(supports, ns, s_lengths_host, nb, cell, 1, w, st);
     if (rc != APR_OK) return rc;
   }
   BatchStarts qb;
@@ -945,11 +986,13 @@ static int radius_async(const float* queries, int64_t nq, const float* supports,
   APR_CHECK_ARG(qs[nb] == nq, "apr_radius_neighbors_async: query batch lengths sum to %d, expected %lld", qs[nb],
                 (long long)nq);
   hipLaunchKernelGGL(k_set_starts, dim3(1), dim3(128), 0, st, qstarts, qb, nb + 1);
-  Grid g{w.keys, w.vals, (uint32_t)(w.cap - 1), w.start, w.sorted, w.mins, radius};
+  Grid g{w.keys, w.vals, (uint32_t)(w.cap - 1), w.start, w.sorted, w.mins, cell};
   APR_HIP(hipMemsetAsync(flags_dev, 0, 8, st));
   hipLaunchKernelGGL(k_radius<2>, dim3((unsigned)cdiv64(nq, 4)), dim3(256), 0, st, queries, nq, qstarts, supports, nb, g,
                      radius * radius, counts, out, (int)limit, out_ld, (int)ns, flags_dev + 1);
-  hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, st, counts, nq, flags_dev);
+  // w.status is the build's word, this call's or (regrid) the one the earlier call left in the scratch: k_radius<2> writes
+  // its overflow flag to flags_dev[1], never there; k_max_int folds it into flags_dev[1]
+  hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, st, counts, nq, flags_dev, (const int*)w.status, flags_dev + 1);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }

@@ -172,6 +172,10 @@ def finish_radius_tables_async(tables, flags_all):
     def then(host):
         done = []
         for t, (maxc, status) in zip(tables, host):
+            if status >= 16:      # 16 + the search grid's build status (csrc/points.hip: k_max_int)
+                raise _lib.AprHipError("apr_radius_neighbors: the search grid could not be built (status "
+                                       f"{int(status) - 16}: 1 / 2 cell map, 3 = the supports of a cloud span too many "
+                                       "cells of 1.01 * radius)")
             if status != 0:
                 raise _lib.AprHipError("apr_radius_neighbors: a query has more neighbours within the radius than the "
                                        "kernel's candidate buffer holds")
