@@ -247,6 +247,9 @@ PROTOTYPES = {
     "apr_dense_argmax": (C.c_int, [_p, _i64, _i64, _p, _p, _p]),
     "apr_ransac_pairs_geometric_scratch_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "apr_ransac_pose_pairs_geometric": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _f64, _i64, _i64, _u64, _p, _sz, _p, _p]),
+    "apr_information_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "apr_information_batch": (C.c_int, [_p, _p, _p, _p, _i32, _p, _i32, _p, _i64, _f64, _p, _p, _p, _p, _sz, _p]),
+    "apr_posegraph_optimize": (C.c_int, [_p, _p, _i32, _p, _p, _i64, _p, _p, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p]),
 }
 
 class KpResnetDesc(C.Structure):

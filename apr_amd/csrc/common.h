@@ -137,6 +137,9 @@ int apr_internal_search_grid(const float* pts, int64_t n, float cell, void* scra
                              hipStream_t st);
 int apr_internal_search_grid_batch(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, float cell, void* scratch,
                                    AprSearchGrid* out, hipStream_t st);
+// icp.hip: k_icp_pack on `st` -- rows[e] = (x, y, z, bits(global row)) of the target rows in bucket order, the layout
+// k_icp_assoc probes; a grid whose status word is set is left alone.  Shared with posegraph.hip.
+int apr_internal_icp_pack(const float* tgt, int64_t m, AprSearchGrid g, float4* rows, hipStream_t st);
 
 __device__ static inline int apr_table_lookup(const unsigned long long* __restrict__ keys,
                                               const int* __restrict__ vals, uint32_t mask,

@@ -281,6 +281,12 @@ static size_t icp_carve(void* scratch, int64_t n, int64_t m, int nb, IcpScratch*
 
 }  // namespace
 
+int apr_internal_icp_pack(const float* tgt, int64_t m, AprSearchGrid g, float4* rows, hipStream_t st) {
+  hipLaunchKernelGGL(k_icp_pack, dim3((unsigned)cdiv64(m, 256)), dim3(256), 0, st, tgt, m, g, rows);
+  APR_LAUNCH_CHECK();
+  return APR_OK;
+}
+
 APR_API size_t apr_icp_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb) {
   IcpScratch s;
   return icp_carve(nullptr, n_src_total, n_tgt_total, nb > 0 ? nb : 1, &s);

@@ -131,3 +131,109 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     rec, corr = ops.icp_batch(src, [0, len(src)], tgt, [0, len(tgt)], init.reshape(1, 4, 4), max_correspondence_distance,
                               criteria.max_iteration, criteria.relative_fitness, criteria.relative_rmse, want_corr=True)
     return icp_results(rec, corr, [0, len(src)])[0]
+
+
+# ---- multiway registration: the open3d calls of FCGF_APR/lib/complement_data_loader.py:417-419 and :425-461 (and
+# Predator_APR/datasets/kitti.py:206-251) on the HIP kernels of csrc/posegraph.hip, with arrays in place of open3d objects.
+# Restated, not recorded: parity with open3d is unpinned.
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation):
+    """o3d.pipelines.registration.get_information_matrix_from_point_clouds -> float64 [6,6] numpy.  Synchronises."""
+    src, tgt = _dev(source), _dev(target)
+    T = np.asarray(transformation, dtype=np.float64).reshape(1, 4, 4)
+    info, _, _ = ops.information_batch(src, [0, len(src)], tgt, [0, len(tgt)], T, max_correspondence_distance)
+    return info[0].cpu().numpy()
+
+
+class PoseGraphNode:
+    def __init__(self, pose=None):
+        self.pose = np.eye(4) if pose is None else np.array(pose, dtype=np.float64).reshape(4, 4)
+
+
+class PoseGraphEdge:
+    def __init__(self, source_node_id=-1, target_node_id=-1, transformation=None, information=None, uncertain=False,
+                 confidence=1.0):
+        self.source_node_id = int(source_node_id)
+        self.target_node_id = int(target_node_id)
+        self.transformation = np.eye(4) if transformation is None else np.array(transformation, dtype=np.float64).reshape(4, 4)
+        self.information = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
+        self.uncertain = bool(uncertain)
+        self.confidence = float(confidence)
+
+
+class PoseGraph:
+    def __init__(self):
+        self.nodes = []
+        self.edges = []
+
+
+class GlobalOptimizationOption:
+    def __init__(self, max_correspondence_distance=0.03, edge_prune_threshold=0.25, preference_loop_closure=1.0,
+                 reference_node=-1):
+        self.max_correspondence_distance = float(max_correspondence_distance)
+        self.edge_prune_threshold = float(edge_prune_threshold)
+        self.preference_loop_closure = float(preference_loop_closure)
+        self.reference_node = int(reference_node)
+
+
+class GlobalOptimizationConvergenceCriteria:
+    """open3d's defaults, the only values the HIP kernel takes (both reference call sites pass none)."""
+    DEFAULTS = dict(max_iteration=100, min_relative_increment=1e-6, min_relative_residual_increment=1e-6,
+                    min_right_term=1e-6, min_residual=1e-6, max_iteration_lm=20, upper_scale_factor=2.0 / 3.0,
+                    lower_scale_factor=1.0 / 3.0)
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError(f"GlobalOptimizationConvergenceCriteria: unknown field {sorted(unknown)}")
+        for name, value in self.DEFAULTS.items():
+            setattr(self, name, type(value)(kw.get(name, value)))
+
+    def is_default(self):
+        return all(getattr(self, name) == value for name, value in self.DEFAULTS.items())
+
+
+class GlobalOptimizationLevenbergMarquardt:
+    """The only method on the HIP kernel; open3d's Gauss-Newton optimiser is out of scope."""
+
+
+def global_optimization(pose_graph, method=None, criteria=None, option=None):
+    """o3d.pipelines.registration.global_optimization(pose_graph, method, criteria, option): Levenberg-Marquardt with the
+    default criteria on the device, two passes with pruning in between.  As open3d does, it updates `pose_graph` in place:
+    node poses, edge confidences (after the first pass) and the pruned uncertain edges removed.  The node poses are NOT
+    compensated for option.reference_node (P_0^-1 P_i, what the reference uses, does not depend on it).  Synchronises.
+    -> dict(iterations (first, second pass), status)."""
+    method = GlobalOptimizationLevenbergMarquardt() if method is None else method
+    criteria = GlobalOptimizationConvergenceCriteria() if criteria is None else criteria
+    option = GlobalOptimizationOption() if option is None else option
+    if not isinstance(method, GlobalOptimizationLevenbergMarquardt):
+        raise NotImplementedError(f"global_optimization: only GlobalOptimizationLevenbergMarquardt runs on the HIP kernel "
+                                  f"(got {type(method).__name__}); Gauss-Newton is out of scope")
+    if not isinstance(criteria, GlobalOptimizationConvergenceCriteria) or not criteria.is_default():
+        raise NotImplementedError("global_optimization: the HIP kernel takes the default "
+                                  "GlobalOptimizationConvergenceCriteria only")
+    if option.reference_node not in (-1, 0):
+        raise NotImplementedError("global_optimization: reference_node other than 0 (or -1, none) is not implemented")
+    n = len(pose_graph.nodes)
+    if n > ops.POSEGRAPH_MAX_NODES:
+        raise NotImplementedError(f"global_optimization: graphs with more than {ops.POSEGRAPH_MAX_NODES} nodes are out of scope")
+    if any(e.confidence != 1.0 for e in pose_graph.edges):
+        raise NotImplementedError("global_optimization: the HIP kernel starts every confidence at 1")
+    if not pose_graph.edges:
+        return dict(iterations=(0, 0), status=ops.POSEGRAPH_NO_WEIGHT)
+    layout = ops.PoseGraphLayout([(n, [(e.source_node_id, e.target_node_id, e.uncertain) for e in pose_graph.edges])])
+    T = np.stack([e.transformation for e in pose_graph.edges])
+    info = np.stack([e.information for e in pose_graph.edges])
+    init = np.stack([nd.pose for nd in pose_graph.nodes])
+    poses, conf, kept, iters, status = ops.posegraph_optimize(layout, T, info, init, option.max_correspondence_distance,
+                                                              option.edge_prune_threshold, option.preference_loop_closure)
+    poses, conf, kept = poses.cpu().numpy(), conf.cpu().numpy(), kept.cpu().numpy()
+    status = int(status.cpu()[0])
+    if status == ops.POSEGRAPH_MALFORMED:
+        raise ValueError("global_optimization: malformed pose graph")
+    for nd, P in zip(pose_graph.nodes, poses):
+        nd.pose = P.copy()
+    for e, c in zip(pose_graph.edges, conf):
+        e.confidence = float(c)
+    pose_graph.edges = [e for e, k in zip(pose_graph.edges, kept) if k]
+    return dict(iterations=tuple(int(v) for v in iters.cpu().numpy()[0]), status=status)

@@ -1886,3 +1886,133 @@ def icp_batch(src, src_offsets, tgt, tgt_offsets, init, max_dist, max_iteration=
                             int(max_iteration), float(relative_fitness), float(relative_rmse), ptr(rec), ptr(corr),
                             ptr(scratch), sb, stream()))
     return rec, corr
+
+
+INFORMATION_SUMS = 10         # APR_INFORMATION_SUMS: n, x, y, z, xx, yy, zz, xy, xz, yz over the matched target rows
+POSEGRAPH_MAX_NODES = 8       # APR_POSEGRAPH_MAX_NODES
+# status of a graph (include/apr_hip.h: apr_posegraph_optimize)
+POSEGRAPH_OK, POSEGRAPH_NO_WEIGHT, POSEGRAPH_NO_WEIGHT_PRUNED, POSEGRAPH_NOT_POSITIVE, POSEGRAPH_MALFORMED = 0, 1, 2, 3, 4
+
+
+def _transform_rows(T, nb, name):
+    """T: float64 GPU tensor [nb, >= 12 columns] (ICP records as they lie) or anything that holds nb 4x4 transforms.
+    -> (contiguous float64 GPU tensor, row stride in doubles)."""
+    if not torch.is_tensor(T):
+        T = torch.from_numpy(np.ascontiguousarray(np.asarray(T, dtype=np.float64)))
+    T = T.to(device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.float64).contiguous()
+    if T.dim() == 3:
+        T = T.reshape(T.shape[0], -1)
+    if T.dim() != 2 or T.shape[0] != nb or T.shape[1] < 12:
+        raise _lib.AprHipError(f"{name}: T must hold {nb} rows of at least 12 doubles (4x4 transforms or ICP records)")
+    return T, int(T.shape[1])
+
+
+def information_batch(src, src_offsets, tgt, tgt_offsets, T, max_dist, tgt_of_problem=None, want_corr=False,
+                      want_sums=False):
+    """get_information_matrix_from_point_clouds of nb problems in ONE library call (apr_information_batch).
+
+    The clouds, offsets and `tgt_of_problem` are icp_batch's.  T: float64 [nb, 4, 4], or the records icp_batch returned as
+    they lie ([nb, 20] on the GPU: no copy, no host round trip).
+    -> (info float64 [nb, 6, 6] on the GPU, components (alpha, beta, gamma, tx, ty, tz);
+        sums float64 [nb, 10] on the GPU (n, x, y, z, xx, yy, zz, xy, xz, yz over the matched target rows) or None;
+        corr int32 [sum n] on the GPU as icp_batch, or None)."""
+    src = _f32(src, "information_batch.src").contiguous()
+    tgt = _f32(tgt, "information_batch.tgt").contiguous()
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.dim() != 2 or tgt.shape[1] != 3:
+        raise _lib.AprHipError("information_batch: src and tgt must be [rows, 3]")
+    so = np.ascontiguousarray(np.asarray(src_offsets, dtype=np.int64))
+    to = np.ascontiguousarray(np.asarray(tgt_offsets, dtype=np.int64))
+    nb, n_tgt = len(so) - 1, len(to) - 1
+    if nb < 1 or n_tgt < 1 or so[-1] != src.shape[0] or to[-1] != tgt.shape[0]:
+        raise _lib.AprHipError("information_batch: the offsets must cover the rows of src / tgt")
+    top = None
+    if tgt_of_problem is not None:
+        top = np.ascontiguousarray(np.asarray(tgt_of_problem, dtype=np.int32))
+        if len(top) != nb:
+            raise _lib.AprHipError("information_batch: one target segment per problem expected")
+    T, stride = _transform_rows(T, nb, "information_batch")
+    lib = _lib_()
+    info = torch.empty((nb, 6, 6), dtype=torch.float64, device=src.device)
+    sums = torch.empty((nb, INFORMATION_SUMS), dtype=torch.float64, device=src.device) if want_sums else None
+    corr = torch.empty(src.shape[0], dtype=torch.int32, device=src.device) if want_corr else None
+    sb = int(lib.apr_information_scratch_bytes(src.shape[0], tgt.shape[0], nb))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=src.device)
+    check(lib.apr_information_batch(ptr(src), so.ctypes.data_as(C.c_void_p), ptr(tgt), to.ctypes.data_as(C.c_void_p), n_tgt,
+                                    None if top is None else top.ctypes.data_as(C.c_void_p), nb, ptr(T), stride,
+                                    float(max_dist), ptr(info), ptr(sums), ptr(corr), ptr(scratch), sb, stream()))
+    return info, sums, corr
+
+
+class PoseGraphLayout:
+    """The integer side of a batch of pose graphs, checked on the host once and kept on the GPU: node / edge offsets and
+    the (source, target, uncertain) rows of apr_posegraph_optimize.  `graphs`: per graph (n_nodes, [(source, target,
+    uncertain), ...]) with local node numbers."""
+
+    def __init__(self, graphs, need_chain=False):
+        node_off, edge_off, rows = [0], [0], []
+        for g, (n, edges) in enumerate(graphs):
+            n, edges = int(n), [(int(s), int(t), int(bool(u))) for s, t, u in edges]
+            if not 1 <= n <= POSEGRAPH_MAX_NODES:
+                raise _lib.AprHipError(f"posegraph: graph {g} has {n} nodes; 1 .. {POSEGRAPH_MAX_NODES} run on the HIP kernel")
+            if len(edges) > n * (n - 1) // 2 or len(set((s, t) for s, t, _ in edges)) != len(edges):
+                raise _lib.AprHipError(f"posegraph: graph {g}: at most one edge per node pair")
+            if any(not 0 <= s < t < n for s, t, _ in edges):
+                raise _lib.AprHipError(f"posegraph: graph {g}: every edge needs 0 <= source < target < {n}")
+            if need_chain and any((j, j + 1) not in set((s, t) for s, t, _ in edges) for j in range(n - 1)):
+                raise _lib.AprHipError(f"posegraph: graph {g}: the odometry chain needs an edge (j, j + 1) for every j")
+            node_off.append(node_off[-1] + n)
+            edge_off.append(edge_off[-1] + len(edges))
+            rows += edges
+        if not graphs:
+            raise _lib.AprHipError("posegraph: no graph")
+        self.ng, self.n_nodes, self.n_edges = len(graphs), node_off[-1], edge_off[-1]
+        self.node_off_host, self.edge_off_host = np.asarray(node_off), np.asarray(edge_off)
+        self.has_chain = need_chain
+        dev = torch.device('cuda', torch.cuda.current_device())
+        packed = np.concatenate([np.asarray(node_off, dtype=np.int32), np.asarray(edge_off, dtype=np.int32),
+                                 np.asarray(rows, dtype=np.int32).reshape(-1)])
+        self._packed = torch.from_numpy(packed).to(dev)                 # one host -> device copy
+        self.node_off = self._packed[: self.ng + 1]
+        self.edge_off = self._packed[self.ng + 1: 2 * self.ng + 2]
+        self.edges = self._packed[2 * self.ng + 2:]
+
+
+def posegraph_optimize(layout, T, info, init_poses=None, max_correspondence_distance=0.075, edge_prune_threshold=0.25,
+                       preference_loop_closure=1.0):
+    """open3d's global_optimization (Levenberg-Marquardt, default criteria) of every graph of `layout` in ONE launch
+    (apr_posegraph_optimize).
+
+    T: float64 [n_edges, 4, 4] or icp_batch's records as they lie ([n_edges, 20] on the GPU).  info: float64 [n_edges, 6, 6]
+    (GPU tensor or array).  init_poses: float64 [n_nodes, 4, 4], or None for the odometry chain.  Does not synchronise.
+    -> (poses float64 [n_nodes, 4, 4], confidence float64 [n_edges] after the first pass, kept int32 [n_edges],
+        iterations int32 [graphs, 2], status int32 [graphs]) on the GPU."""
+    if not isinstance(layout, PoseGraphLayout):
+        raise _lib.AprHipError("posegraph_optimize: layout must be a PoseGraphLayout")
+    if layout.n_edges < 1:
+        raise _lib.AprHipError("posegraph_optimize: no edge in the batch")
+    T, stride = _transform_rows(T, layout.n_edges, "posegraph_optimize")
+    dev = T.device
+    if not torch.is_tensor(info):
+        info = torch.from_numpy(np.ascontiguousarray(np.asarray(info, dtype=np.float64)))
+    info = info.to(device=dev, dtype=torch.float64).contiguous()
+    if info.numel() != layout.n_edges * 36:
+        raise _lib.AprHipError(f"posegraph_optimize: info must hold {layout.n_edges} 6x6 matrices")
+    if init_poses is None:
+        if not layout.has_chain:
+            raise _lib.AprHipError("posegraph_optimize: without init_poses the layout must be built with need_chain=True")
+    else:
+        if not torch.is_tensor(init_poses):
+            init_poses = torch.from_numpy(np.ascontiguousarray(np.asarray(init_poses, dtype=np.float64)))
+        init_poses = init_poses.to(device=dev, dtype=torch.float64).contiguous()
+        if init_poses.numel() != layout.n_nodes * 16:
+            raise _lib.AprHipError(f"posegraph_optimize: init_poses must hold {layout.n_nodes} 4x4 poses")
+    poses = torch.empty((layout.n_nodes, 4, 4), dtype=torch.float64, device=dev)
+    conf = torch.empty(layout.n_edges, dtype=torch.float64, device=dev)
+    kept = torch.empty(layout.n_edges, dtype=torch.int32, device=dev)
+    iters = torch.empty((layout.ng, 2), dtype=torch.int32, device=dev)
+    status = torch.empty(layout.ng, dtype=torch.int32, device=dev)
+    check(_lib_().apr_posegraph_optimize(ptr(layout.node_off), ptr(layout.edge_off), layout.ng, ptr(layout.edges), ptr(T),
+                                         stride, ptr(info), ptr(init_poses), float(max_correspondence_distance),
+                                         float(edge_prune_threshold), float(preference_loop_closure), ptr(poses), ptr(conf),
+                                         ptr(kept), ptr(iters), ptr(status), stream()))
+    return poses, conf, kept, iters, status

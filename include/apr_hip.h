@@ -1106,6 +1106,61 @@ int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const float* 
                                     int64_t n_pairs, double max_dist, int64_t max_iter, int64_t max_validation, uint64_t seed,
                                     void* scratch, size_t scratch_bytes, double* result_host, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Multiway registration, the default route to the poses of the aggregated point cloud (use_old_pose and not
+ * debug_use_old_complement): FCGF_APR/lib/complement_data_loader.py:408-516 (pairwise_registration, full_registration,
+ * multiway_registration), Predator_APR/datasets/kitti.py:197-297.  PARITY UNPINNED (open3d is not part of this build): both
+ * entries implement the restatement of DESIGN section 19.
+ * ------------------------------------------------------------------------ */
+
+/* o3d.pipelines.registration.get_information_matrix_from_point_clouds(source, target, max_dist, T)
+ * (complement_data_loader.py:417-419, kitti.py:207-209) for nb problems in ONE call.  src / offsets / tgt / segments /
+ * tgt_of_problem_host / nb as apr_icp_batch.  T f64 on the device, problem i at T + i * t_stride (row-major 4x4, the first 12
+ * doubles are read; t_stride >= 12): apr_icp_batch's result records as they lie with t_stride = APR_ICP_RECORD_DOUBLES.
+ * Association = apr_icp_batch's evaluation step with its arithmetic contract: p = fl32(T s) from the original fp32 row,
+ * d^2 in fp32 with every operation rounded, d^2 < fl32(max_dist)^2 strictly, ties to the smallest target row; search-grid
+ * cell 1.01 * max_dist, APR_ERANGE from the grid's status word (nothing is written then).
+ * sums f64[nb, APR_INFORMATION_SUMS] (may be NULL) over the matched TARGET rows (x, y, z) -- the target's own coordinates,
+ * products in fp64 from the fp32 values --: n, x, y, z, xx, yy, zz, xy, xz, yz.  Fixed order (xor butterfly per wave,
+ * (w0 + w1) + (w2 + w3) per workgroup, the partial rows of a problem by one workgroup), no atomics: the same bits run to run
+ * and for a problem alone or inside a batch.
+ * info f64[nb,36] = Lambda row-major, components (alpha, beta, gamma, tx, ty, tz) = sum G^T G over g1 = (0, z, -y, 1, 0, 0),
+ * g2 = (-z, 0, x, 0, 1, 0), g3 = (y, -x, 0, 0, 0, 1): rotation block [[yy + zz, -xy, -xz], [-xy, xx + zz, -yz],
+ * [-xz, -yz, xx + yy]], translation block n I, rotation-translation block [[0, -z, y], [z, 0, -x], [-y, x, 0]] and its
+ * transpose.  No correspondence: Lambda = 0.  corr i32[total source rows] (may be NULL) as apr_icp_batch.
+ * Synchronises `stream` (the grid's status word). */
+#define APR_INFORMATION_SUMS 10
+size_t apr_information_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb);
+int apr_information_batch(const float* src, const int64_t* src_offsets_host, const float* tgt, const int64_t* tgt_offsets_host,
+                          int32_t n_tgt, const int32_t* tgt_of_problem_host, int32_t nb, const double* T, int64_t t_stride,
+                          double max_dist, double* info, double* sums, int32_t* corr, void* scratch, size_t scratch_bytes,
+                          void* stream);
+
+/* o3d.pipelines.registration.global_optimization(pose_graph, GlobalOptimizationLevenbergMarquardt(),
+ * GlobalOptimizationConvergenceCriteria(), GlobalOptimizationOption(max_correspondence_distance, edge_prune_threshold,
+ * reference_node = 0)) (complement_data_loader.py:453-461, kitti.py:243-251) for ng graphs in ONE launch, one workgroup per
+ * graph, fp64 throughout; every pointer is a device pointer.  Graph g owns nodes node_offsets[g] .. [g + 1] (1 .. 8) and
+ * edges edge_offsets[g] .. [g + 1] (0 .. 28).  edges i32[n_edges, 3] = (source, target, uncertain) with LOCAL node numbers,
+ * source < target.  Edge e: transform at T + e * t_stride (row-major 4x4, 12 doubles read; ICP records as they lie with
+ * t_stride = APR_ICP_RECORD_DOUBLES), information matrix info[e * 36 ..].  init_poses f64[n_nodes, 16], or NULL: the
+ * odometry chain P_0 = I, odo <- T_(j,j+1) odo, P_(j+1) = odo^-1 (:426-438), which needs an edge (j, j + 1) for every j.
+ * The algorithm (error vector, Jacobian, line process, LM loop, default criteria, pruning and the second pass) is DESIGN
+ * section 19.  H and b are assembled by one owner thread per entry over the edges in ascending order, no atomics: a graph
+ * gives the same bits alone or in a batch, and run to run.  reference_node compensation is NOT applied; P_0^-1 P_i, the only
+ * product the callers use (:508-509), does not depend on it.
+ * poses f64[n_nodes,16]; confidence f64[n_edges] after the FIRST pass (1 for certain edges); kept i32[n_edges] (0 = pruned);
+ * iterations i32[ng,2] (outer iterations of both passes); status i32[ng]: 0 ok, 1 line-process weight mu = 0 (every Lambda(5,5)
+ * zero or no edge: the initial poses are returned, no division), 2 the same after pruning (first-pass poses), 3 a pivot of
+ * the damped system was not positive and finite (poses of the last accepted step), 4 malformed graph (node / edge counts,
+ * an edge outside source < target < n, a missing odometry edge without init_poses: nothing else of that graph is written).
+ * Does not synchronise. */
+#define APR_POSEGRAPH_MAX_NODES 8
+int apr_posegraph_optimize(const int32_t* node_offsets, const int32_t* edge_offsets, int32_t ng, const int32_t* edges,
+                           const double* T, int64_t t_stride, const double* info, const double* init_poses,
+                           double max_correspondence_distance, double edge_prune_threshold, double preference_loop_closure,
+                           double* poses, double* confidence, int32_t* kept, int32_t* iterations, int32_t* status,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
