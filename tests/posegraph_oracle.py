@@ -109,7 +109,8 @@ def edge_error(e, P):
 
 def edge_jacobian(e, P):
     X = e.Ti @ np.linalg.inv(P[e.t])
-    return np.stack([lin(X @ Om @ P[e.s]) for Om in GENERATORS], 1)
+    Js = np.stack([lin(X @ Om @ P[e.s]) for Om in GENERATORS], 1)
+    return Js
 
 
 def odometry_chain(n, edges):
@@ -122,8 +123,8 @@ def odometry_chain(n, edges):
     return P
 
 
-def _mu(edges, mcd):
-    return PREFERENCE * mcd * mcd * float(np.mean([e.info[5, 5] for e in edges])) if edges else 0.0
+def _mu(edges, mcd, preference=PREFERENCE):
+    return preference * mcd * mcd * float(np.mean([e.info[5, 5] for e in edges])) if edges else 0.0
 
 
 def _residual(errs, edges, conf, mu):
@@ -151,30 +152,64 @@ def _system(P, edges, conf):
     return H, b
 
 
-def optimize_once(P, edges, conf, mcd):
-    """One LM optimisation.  -> (poses, confidences, outer iterations), or None when mu = 0."""
-    mu = _mu(edges, mcd)
-    if not (mu > 0.0):
-        return None
+def _positive_definite(A):
+    """The status-3 rule of DESIGN section 19.2: a Cholesky factorisation whose pivots are all positive and finite."""
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return False
+    return bool(np.isfinite(L.diagonal()).all() and (L.diagonal() > 0.0).all())
+
+
+def _optimize(P, edges, conf, mu, trace):
+    """One LM optimisation with mu > 0.  -> (poses, confidences, outer iterations, failed).  `failed`: H + lambda I was not
+    positive definite (status 3); the poses and confidences are those of the last accepted step.
+    `trace` (dict) receives `steps`, one dict per inner pass, and `decisions`, one (name, outer iteration, inner count, lhs,
+    rhs) per comparison the contract makes: max_b (lhs < rhs stops), delta (lhs < rhs stops), rho (lhs > rhs accepts),
+    decrease and residual (lhs < rhs stops)."""
+    steps, dec = trace.setdefault("steps", []), trace.setdefault("decisions", [])
     P, conf = [p.copy() for p in P], list(conf)
     errs = [edge_error(e, P) for e in edges]
     cur = _residual(errs, edges, conf, mu)
     H, b = _system(P, edges, conf)
     lam, ni = 1e-5 * H.diagonal().max(), 2.0
+    dec.append(("max_b", -1, 0, float(b.max()), MIN))
     stop = b.max() < MIN
+    failed = False
+    # The factorisation reads the LOWER triangle of H + lambda I (DESIGN section 19.2).  With every Lambda symmetric H is
+    # symmetric up to rounding and the full matrix goes to the solver, as it always did; an unsymmetric Lambda makes
+    # A_e = Js^T Lambda Js, and with it H, unsymmetric by more than rounding, and then the lower triangle is mirrored first.
+    mirror = any(not np.array_equal(e.info, e.info.T) for e in edges)
     it = 0
     while it < MAX_ITERATION and not stop:
         count, rho = 0, 0.0
         while True:
-            d = np.linalg.solve(H + lam * np.eye(len(b)), b)
-            x = np.concatenate([vec(p) for p in P])
-            stop = stop or np.linalg.norm(d) < MIN * (np.linalg.norm(x) + MIN)
+            step = dict(outer=it, count=count, lam_before=lam, lam_after=lam, cur=cur, new=None, den=None, rho=None,
+                        accepted=False, failed=False)
+            steps.append(step)
+            A = H + lam * np.eye(len(b))
+            if mirror:
+                A = np.tril(A) + np.tril(A, -1).T
+            if not _positive_definite(A):
+                failed = stop = step["failed"] = True
+                w = np.linalg.eigvalsh(A, UPLO="L")                # the lower triangle, as the factorisation reads it
+                step["eigenvalues"] = (float(w.min()), float(w.max()))
+            else:
+                d = np.linalg.solve(A, b)
+                x = np.concatenate([vec(p) for p in P])
+                dec.append(("delta", it, count, float(np.linalg.norm(d)), MIN * (float(np.linalg.norm(x)) + MIN)))
+                stop = stop or np.linalg.norm(d) < MIN * (np.linalg.norm(x) + MIN)
             if not stop:
                 Pn = [mat(d[6 * i:6 * i + 6]) @ P[i] for i in range(len(P))]
                 errs_n = [edge_error(e, Pn) for e in edges]
                 new = _residual(errs_n, edges, conf, mu)
-                rho = (cur - new) / (d @ (lam * d + b) + 1e-3)
+                den = d @ (lam * d + b)
+                rho = (cur - new) / (den + 1e-3)
+                dec.append(("rho", it, count, float(rho), 0.0))
+                step.update(new=new, den=float(den), rho=float(rho), accepted=bool(rho > 0))
                 if rho > 0:
+                    dec.append(("decrease", it, count, cur - new, MIN * cur))
+                    dec.append(("residual", it, count, new, MIN))
                     stop = stop or (cur - new < MIN * cur) or (new < MIN)
                     P = Pn
                     lam *= max(1.0 / 3.0, min(1.0 - (2.0 * rho - 1.0) ** 3, 2.0 / 3.0))
@@ -182,37 +217,60 @@ def optimize_once(P, edges, conf, mcd):
                     cur = new
                     conf = [(mu / (mu + float(er @ e.info @ er))) ** 2 if e.uncertain else l
                             for e, er, l in zip(edges, errs_n, conf)]
+                    errs = errs_n
                     H, b = _system(P, edges, conf)
+                    dec.append(("max_b", it, count, float(b.max()), MIN))
                     stop = stop or b.max() < MIN
                 else:
                     lam *= ni
                     ni *= 2.0
+                step["lam_after"] = lam
             count += 1
             stop = stop or count > MAX_ITERATION_LM
             if rho > 0 or stop:
                 break
         it += 1
-    return P, conf, it
+    return P, conf, it, failed
 
 
-def global_optimization(n, edges, mcd, init=None):
-    """-> dict(poses [n] of [4,4], confidence [ne] after the first pass, kept bool [ne], iterations (2), status)."""
+def optimize_once(P, edges, conf, mcd, preference=PREFERENCE, trace=None):
+    """One LM optimisation.  -> (poses, confidences, outer iterations), or None when mu = 0."""
+    mu = _mu(edges, mcd, preference)
+    if not (mu > 0.0):
+        return None
+    return _optimize(P, edges, conf, mu, {} if trace is None else trace)[:3]
+
+
+def global_optimization(n, edges, mcd, init=None, edge_prune_threshold=PRUNE, preference_loop_closure=PREFERENCE):
+    """-> dict(poses [n] of [4,4], confidence [ne] after the first pass, kept bool [ne], iterations (2), status, trace).
+    trace: dict(passes = the traces of the passes that ran (see _optimize), prune = (confidence, threshold) of every
+    uncertain edge after the first pass).  Status 3: the pass stops at the solve that failed and
+    counts that outer iteration; after the first pass the confidences and flags are still those of its last accepted step."""
     P0 = [np.array(p, dtype=np.float64) for p in init] if init is not None else odometry_chain(n, edges)
-    out = dict(poses=P0, confidence=np.ones(len(edges)), kept=np.ones(len(edges), dtype=bool), iterations=(0, 0), status=0)
-    first = optimize_once(P0, edges, [1.0] * len(edges), mcd)
-    if first is None:
+    trace = dict(passes=[], prune=[])
+    out = dict(poses=P0, confidence=np.ones(len(edges)), kept=np.ones(len(edges), dtype=bool), iterations=(0, 0), status=0,
+               trace=trace)
+    mu1 = _mu(edges, mcd, preference_loop_closure)
+    if not (mu1 > 0.0):
         out["status"] = 1
         return out
-    P1, conf1, it1 = first
+    trace["passes"].append({})
+    P1, conf1, it1, failed = _optimize(P0, edges, [1.0] * len(edges), mu1, trace["passes"][0])
     conf1 = np.array([c if e.uncertain else 1.0 for e, c in zip(edges, conf1)])
-    kept = np.array([not (e.uncertain and c < PRUNE) for e, c in zip(edges, conf1)])
-    sub = [e for e, k in zip(edges, kept) if k]
-    second = optimize_once(P1, sub, [c for c, k in zip(conf1, kept) if k], mcd)
+    trace["prune"] = [(float(c), edge_prune_threshold) for e, c in zip(edges, conf1) if e.uncertain]
+    kept = np.array([not (e.uncertain and c < edge_prune_threshold) for e, c in zip(edges, conf1)])
     out.update(poses=P1, confidence=conf1, kept=kept, iterations=(it1, 0))
-    if second is None:
+    if failed:
+        out["status"] = 3
+        return out
+    sub = [e for e, k in zip(edges, kept) if k]
+    mu2 = _mu(sub, mcd, preference_loop_closure)
+    if not (mu2 > 0.0):
         out["status"] = 2
         return out
-    out.update(poses=second[0], iterations=(it1, second[2]))
+    trace["passes"].append({})
+    P2, _, it2, failed = _optimize(P1, sub, [c for c, k in zip(conf1, kept) if k], mu2, trace["passes"][1])
+    out.update(poses=P2, iterations=(it1, it2), status=3 if failed else 0)
     return out
 
 
