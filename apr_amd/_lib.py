@@ -186,6 +186,10 @@ PROTOTYPES = {
     "apr_grid_subsample_scratch_bytes": (_sz, [_i64]),
     "apr_grid_subsample": (C.c_int, [_p, _i64, _p, _i32, _f32, _p, _i32, _p, _p, _p, _p, _sz, _p]),
     "apr_grid_subsample_async": (C.c_int, [_p, _i64, _p, _i32, _f32, _p, _i32, _p, _p, _p, _p, _sz, _p]),
+    "apr_voxel_down_sample_scratch_bytes": (_sz, [_i64]),
+    "apr_voxel_down_sample": (C.c_int, [_p, _i64, _p, _i32, _f64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "apr_sample_augment": (C.c_int, [_p, _p, _i64, _f64, _p, _f64, _p, _p, _p]),
+    "apr_cloud_mean": (C.c_int, [_p, _i64, _p, _p]),
     "apr_radius_scratch_bytes": (_sz, [_i64, _i64]),
     "apr_radius_neighbors_async": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _f32, _i32, _p, _i64, _p, _p, _sz, _p]),
     "apr_radius_neighbors_regrid_async": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _f32, _i32, _p, _i64, _p, _p, _sz, _p]),

@@ -137,6 +137,25 @@ int apr_internal_search_grid(const float* pts, int64_t n, float cell, void* scra
                              hipStream_t st);
 int apr_internal_search_grid_batch(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, float cell, void* scratch,
                                    AprSearchGrid* out, hipStream_t st);
+// points.hip: the same bucket build over cell coordinates of the caller's own making (voxel.hip).  Between _begin and
+// _finish the caller's kernel writes coords[i] = (cloud, ix, iy, iz) for every row; a row whose coordinates leave the
+// packed-key range belongs to no cell and sets the status word to 1.
+struct AprCellBuckets {
+  int4* coords;              // [n]   to be written by the caller
+  const int* starts;         // [nb + 1] first row of every cloud
+  const float* mins;         // [nb, 3] per-cloud minimum
+  const int4* cell_coords;   // [n_cells] cells in ascending order of their first row
+  const int* n_cells;
+  const int* status;
+  const int* start;          // [n_cells + 1]
+  int* sorted;               // rows bucketed by cell, in no particular order inside a cell
+  int* big_count;            // one zeroed word and n ints for a list of the caller's (crowded cells)
+  int* big_list;
+  int* spare;                // 64 ints, free after _finish
+};
+int apr_internal_buckets_begin(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, void* scratch,
+                               AprCellBuckets* out, hipStream_t st);
+int apr_internal_buckets_finish(int64_t n, void* scratch, int64_t* first, hipStream_t st);
 // icp.hip: k_icp_pack on `st` -- rows[e] = (x, y, z, bits(global row)) of the target rows in bucket order, the layout
 // k_icp_assoc probes; a grid whose status word is set is left alone.  Shared with posegraph.hip.
 int apr_internal_icp_pack(const float* tgt, int64_t m, AprSearchGrid g, float4* rows, hipStream_t st);

@@ -887,6 +887,52 @@ int apr_internal_search_grid_batch(const float* pts, int64_t n, const int32_t* l
   return APR_OK;
 }
 
+// internal: the bucket build over cell coordinates that the CALLER computes (voxel.hip: open3d's float64 grid).  _begin
+// carves `scratch` (apr_internal_grid_bytes(n)), uploads the cloud offsets and takes the per-cloud minima; the caller's
+// kernel then fills out->coords; _finish runs build_grid's tail on them -- apr_map_build (cells in first-occurrence
+// order, their first rows to `first`), count / scan / fill -- with the kernels above, unchanged.
+int apr_internal_buckets_begin(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, void* scratch,
+                               AprCellBuckets* out, hipStream_t st) {
+  GridWork w = carve(scratch, n);
+  BatchStarts bs;
+  bs.v[0] = 0;
+  for (int b = 0; b < nb; ++b) bs.v[b + 1] = bs.v[b] + lengths_host[b];
+  APR_CHECK_ARG(bs.v[nb] == n, "batch lengths sum to %d, expected %lld points", bs.v[nb], (long long)n);
+  hipLaunchKernelGGL(k_set_starts, dim3(1), dim3(128), 0, st, w.starts_dev, bs, nb + 1);
+  hipLaunchKernelGGL(k_cloud_min, dim3(nb), dim3(kMinThreads), 0, st, pts, w.starts_dev, nb, w.mins);
+  APR_LAUNCH_CHECK();
+  out->coords = w.coords;
+  out->starts = w.starts_dev;
+  out->mins = w.mins;
+  out->cell_coords = w.cell_coords;
+  out->n_cells = w.n_cells;
+  out->status = w.status;
+  out->start = w.start;
+  out->sorted = w.sorted;
+  out->big_count = w.big;
+  out->big_list = w.cnt;
+  out->spare = w.cursor;
+  return APR_OK;
+}
+
+int apr_internal_buckets_finish(int64_t n, void* scratch, int64_t* first, hipStream_t st) {
+  GridWork w = carve(scratch, n);
+  int rc = apr_map_build((const int32_t*)w.coords, n, nullptr, 0, (uint64_t*)w.keys, w.vals, w.cap,
+                         (int32_t*)w.cell_coords, first, w.n_cells, w.status, w.map_scratch, w.map_scratch_bytes, st);
+  if (rc != APR_OK) return rc;
+  APR_HIP(hipMemsetAsync(w.cnt, 0, n * 4, st));
+  APR_HIP(hipMemsetAsync(w.cursor, 0, n * 4, st));
+  const unsigned nblk = (unsigned)cdiv64(n, kBlock);
+  hipLaunchKernelGGL(k_cell_of, dim3(nblk), dim3(kBlock), 0, st, w.coords, n, w.keys, w.vals, (uint32_t)(w.cap - 1), 0,
+                     w.cell, w.cnt, w.status);
+  const unsigned nscan = (unsigned)cdiv64(n, kScanBlock);
+  hipLaunchKernelGGL(k_scan_sums, dim3(nscan), dim3(256), 0, st, w.cnt, w.n_cells, w.sorted);
+  hipLaunchKernelGGL(k_scan_apply, dim3(nscan), dim3(256), 0, st, w.cnt, w.n_cells, w.sorted, w.start, w.big);
+  hipLaunchKernelGGL(k_fill, dim3(nblk), dim3(kBlock), 0, st, w.cell, n, w.start, w.cursor, w.sorted);
+  APR_LAUNCH_CHECK();
+  return APR_OK;
+}
+
 APR_API size_t apr_radius_scratch_bytes(int64_t nq, int64_t ns) {
   return grid_work_bytes(ns > 0 ? ns : 1) + align256((nq > 0 ? nq : 1) * 4) + align256((kMaxBatch + 1) * 4) + 512;
 }

@@ -237,3 +237,14 @@ def global_optimization(pose_graph, method=None, criteria=None, option=None):
         e.confidence = float(c)
     pose_graph.edges = [e for e, k in zip(pose_graph.edges, kept) if k]
     return dict(iterations=tuple(int(v) for v in iters.cpu().numpy()[0]), status=status)
+
+
+# ---- voxel centroids: open3d's PointCloud.voxel_down_sample as Predator_APR's loaders call it (datasets/kitti.py:464-475,
+# 588-589, the same lines of nuscenes.py) on the HIP kernels of csrc/voxel.hip.  Restated, not recorded (DESIGN section
+# 20): the contract is exact against tests/voxel_oracle.py, parity with open3d itself is unpinned.
+
+def voxel_down_sample(points, voxel_size):
+    """o3d.geometry.PointCloud(points).voxel_down_sample(voxel_size).points for an [N,3] array / tensor: the float64
+    centroids [M,3] on the GPU, voxels in ascending order of their first row.  Synchronises."""
+    out, _ = ops.voxel_down_sample(_dev(points), [len(points)], voxel_size, want=("centroid",))
+    return out["centroid"]

@@ -2016,3 +2016,67 @@ def posegraph_optimize(layout, T, info, init_poses=None, max_correspondence_dist
                                          float(edge_prune_threshold), float(preference_loop_closure), ptr(poses), ptr(conf),
                                          ptr(kept), ptr(iters), ptr(status), stream()))
     return poses, conf, kept, iters, status
+
+
+# ----------------------------------------------------------------------------
+# training samples on the device (csrc/voxel.hip)
+# ----------------------------------------------------------------------------
+
+VOXEL_OUTPUTS = ("centroid", "centroid32", "count", "first", "index")
+VOXEL_MAX_INDEX = 131071      # per axis: the packed voxel key's range (csrc/common.h), indices are >= 0 by construction
+
+
+def voxel_down_sample(points, lengths, voxel_size, want=("centroid", "centroid32")):
+    """open3d's voxel_down_sample of a batch of clouds in ONE library call (apr_voxel_down_sample, include/apr_hip.h).
+
+    points f32 [n,3] on the GPU (clouds concatenated), `lengths` host int32 [nb].  `want`: which of centroid (f64 [n',3]),
+    centroid32 (f32 [n',3]), count (i32 [n']), first (i32 [n'], the voxel's first row in `points`), index (i32 [n',3])
+    to compute.  Rows are grouped by cloud in batch order, inside a cloud by ascending first row.
+    -> (dict of the wanted GPU tensors, voxels per cloud as int32 numpy [nb]).  Synchronises."""
+    points = _f32(points, "voxel_down_sample.points").contiguous()
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.AprHipError("voxel_down_sample: points must be [n, 3]")
+    unknown = set(want) - set(VOXEL_OUTPUTS)
+    if unknown:
+        raise _lib.AprHipError(f"voxel_down_sample: unknown outputs {sorted(unknown)}; choose from {VOXEL_OUTPUTS}")
+    n = points.shape[0]
+    la = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+    dev = points.device
+    shapes = {"centroid": ((n, 3), torch.float64), "centroid32": ((n, 3), torch.float32), "count": ((n,), torch.int32),
+              "first": ((n,), torch.int32), "index": ((n, 3), torch.int32)}
+    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in VOXEL_OUTPUTS if k in want}
+    lib = _lib_()
+    sb = int(lib.apr_voxel_down_sample_scratch_bytes(n))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+    out_len = np.zeros(len(la), np.int32)
+    check(lib.apr_voxel_down_sample(ptr(points), n, la.ctypes.data_as(C.c_void_p), len(la), float(voxel_size),
+                                    *[ptr(out.get(k)) for k in VOXEL_OUTPUTS], out_len.ctypes.data_as(C.c_void_p),
+                                    ptr(scratch), sb, stream()))
+    m = int(out_len.sum())
+    return {k: v[:m] for k, v in out.items()}, out_len
+
+
+def sample_augment(points, u, noise, rot, scale, shift):
+    """Predator_APR's augmentation of one side (apr_sample_augment): points f64 [n,3] and u f64 [n,3] on the GPU,
+    rot float64 [3,3] or None, shift float64 [3]  ->  f32 [n,3]: (R (p + (u - 0.5) noise)) scale + shift, rounded once."""
+    if not (points.is_cuda and points.dtype == torch.float64 and u.is_cuda and u.dtype == torch.float64) \
+            or points.shape != u.shape or points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.AprHipError("sample_augment: points and u must be float64 [n,3] GPU tensors of one shape")
+    points, u = points.contiguous(), u.contiguous()
+    R = None if rot is None else np.ascontiguousarray(np.asarray(rot, dtype=np.float64).reshape(9))
+    s = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(3))
+    out = torch.empty(points.shape, dtype=torch.float32, device=points.device)
+    check(_lib_().apr_sample_augment(ptr(points), ptr(u), points.shape[0], float(noise),
+                                     None if R is None else R.ctypes.data_as(C.c_void_p), float(scale),
+                                     s.ctypes.data_as(C.c_void_p), ptr(out), stream()))
+    return out
+
+
+def cloud_mean(points):
+    """float64 [3] mean of the rows of an f32 [n,3] GPU cloud, the same bits from run to run (apr_cloud_mean)."""
+    points = _f32(points, "cloud_mean.points").contiguous()
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise _lib.AprHipError("cloud_mean: points must be [n >= 1, 3]")
+    out = torch.empty(3, dtype=torch.float64, device=points.device)
+    check(_lib_().apr_cloud_mean(ptr(points), points.shape[0], ptr(out), stream()))
+    return out

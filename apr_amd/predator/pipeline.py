@@ -51,11 +51,16 @@ class HostPending:
 
 class PredatorRegistration:
     def __init__(self, model, config, neighborhood_limits, voxel_size=0.3, n_points=5000, distance_threshold=0.3,
-                 max_iteration=50000, max_validation=1000):
+                 max_iteration=50000, max_validation=1000, voxelizer='grid'):
         """`neighborhood_limits`: per-level caps of the radius neighbourhoods (the reference calibrates them once per
         dataset, datasets/dataloader.py:calibrate_neighbors); `n_points`: interest points kept per frame
-        (configs/test/kitti.yaml n_points)."""
+        (configs/test/kitti.yaml n_points); `voxelizer`: 'grid' feeds the network the barycentres of apr_grid_subsample
+        (the grid of the KPConv pyramid), 'open3d' the centroids of the loader's own voxel_down_sample
+        (datasets/kitti.py:588-589; apr_voxel_down_sample, rounded to fp32 once)."""
         _host.limit_cpu_threads()
+        if voxelizer not in ('grid', 'open3d'):
+            raise ValueError(f"PredatorRegistration: voxelizer must be 'grid' or 'open3d', got {voxelizer!r}")
+        self.voxelizer = voxelizer
         self.model = model.eval()
         self.config = config
         self.limits = list(neighborhood_limits)
@@ -64,12 +69,20 @@ class PredatorRegistration:
         self.distance_threshold = float(distance_threshold)
         self.max_iteration, self.max_validation = int(max_iteration), int(max_validation)
 
+    def _voxelise(self, points, lens):
+        """-> (fp32 points of the voxelised clouds, their lengths) by the configured voxelizer."""
+        if self.voxelizer == 'open3d':
+            from .. import ops
+            out, sub = ops.voxel_down_sample(points, lens, self.voxel_size, want=("centroid32",))
+            return out["centroid32"], sub
+        return point_ops.grid_subsample(points, lens, self.voxel_size)
+
     @torch.no_grad()
     def encode(self, xyz0, xyz1):
         """-> (src points, tgt points, features [n0+n1, C], overlap scores, saliency scores)."""
         dev = xyz0.device
         lens = np.array([len(xyz0), len(xyz1)], np.int32)
-        pts, lens = point_ops.grid_subsample(torch.cat([xyz0, xyz1]), lens, self.voxel_size)
+        pts, lens = self._voxelise(torch.cat([xyz0, xyz1]), lens)
         src, tgt = pts[:lens[0]], pts[lens[0]:]
         ones = lambda p: torch.ones((len(p), 1), device=dev)
         batch = collate_fn_descriptor([(src, tgt, ones(src), ones(tgt))], self.config, self.limits)
@@ -84,7 +97,7 @@ class PredatorRegistration:
         dev = pairs[0][0].device
         clouds = [c for pair in pairs for c in pair]
         lens = np.array([len(c) for c in clouds], np.int32)
-        pts, lens = point_ops.grid_subsample(torch.cat(clouds), lens, self.voxel_size)
+        pts, lens = self._voxelise(torch.cat(clouds), lens)
         ends = np.cumsum(lens)
         sub = [pts[e - n:e] for e, n in zip(ends, lens)]
         ones = lambda p: torch.ones((len(p), 1), device=dev)
@@ -114,10 +127,13 @@ class PredatorRegistration:
         seeds = list(range(len(pairs))) if seeds is None else list(seeds)
         dev = pairs[0][0].device
         clouds = [c for pair in pairs for c in pair]
-        sub0 = point_ops.grid_subsample_async(torch.cat(clouds), np.array([len(c) for c in clouds], np.int32),
-                                              self.voxel_size)
-        yield sub0.fetch
-        pts, lens = sub0.finish()
+        if self.voxelizer == 'open3d':      # apr_voxel_down_sample has no synchronisation-free form
+            pts, lens = self._voxelise(torch.cat(clouds), np.array([len(c) for c in clouds], np.int32))
+        else:
+            sub0 = point_ops.grid_subsample_async(torch.cat(clouds), np.array([len(c) for c in clouds], np.int32),
+                                                  self.voxel_size)
+            yield sub0.fetch
+            pts, lens = sub0.finish()
         ends = np.cumsum(lens)
         sub = [pts[e - n:e] for e, n in zip(ends, lens)]
         ones = lambda p: torch.ones((len(p), 1), device=dev)

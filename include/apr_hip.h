@@ -670,6 +670,37 @@ int apr_grid_subsample_async(const float* pts, int64_t n, const int32_t* lengths
                              const float* feats, int32_t fdim, float* out_pts, float* out_feats,
                              int32_t* lengths_status_dev, void* scratch, size_t scratch_bytes, void* stream);
 
+/* open3d's voxel centroids of a batch of clouds; replaces
+ *   open3d.geometry.PointCloud.voxel_down_sample(voxel_size=) as the loaders call it
+ *   (Predator_APR/datasets/kitti.py:464-475,588-589 and the same lines of datasets/nuscenes.py).
+ *   pts f32[n,3] (clouds concatenated), lengths_host i32[nb] (HOST, 1 <= nb <= 64, every length > 0).
+ *   Per cloud and axis, float64 with every operation rounded on its own:
+ *     origin = (double)min - voxel_size * 0.5;  index = floor(((double)p - origin) / voxel_size);
+ *     sum = 0.0, sum += (double)p over the voxel's rows in ascending row order;  centroid = sum / (double)count.
+ *   Output rows: clouds in batch order, inside a cloud the voxels in ascending order of their first row.
+ *   centroid f64[<=n,3], centroid32 f32[<=n,3] (the centroid rounded to nearest once), count i32[<=n],
+ *   first i32[<=n] (the voxel's first row in pts), index i32[<=n,3]; out_lengths_host i32[nb] (HOST): voxels per
+ *   cloud.  Any of the six may be NULL; the device arrays must hold n rows.  A cloud gives the same bits alone and
+ *   inside a batch, and from run to run.  APR_ERANGE (outputs undefined): a row is not finite, or an index exceeds
+ *   131071.  Synchronises the stream. */
+size_t apr_voxel_down_sample_scratch_bytes(int64_t n);
+int apr_voxel_down_sample(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, double voxel_size,
+                          double* centroid, float* centroid32, int32_t* count, int32_t* first, int32_t* index,
+                          int32_t* out_lengths_host, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The augmentation of a Predator_APR sample on its float64 centroids; replaces
+ *   Predator_APR/datasets/kitti.py:494-517 (noise, rotation of one side, scale, shift) and the `.float()` of
+ *   datasets/dataloader.py:163.  pts f64[n,3], u f64[n,3] (the loader's np.random.rand draws) on the device;
+ *   rot_host f64[9] row-major (HOST; NULL: this side does not rotate), shift_host f64[3] (HOST).
+ *     q = p + (u - 0.5) * noise;  q_j = (R[j,0]*q_0 + R[j,1]*q_1) + R[j,2]*q_2;  out = (float)(q * scale + shift),
+ *   every operation a separately rounded float64 operation, one rounding to fp32 at the end. */
+int apr_sample_augment(const double* pts, const double* u, int64_t n, double noise, const double* rot_host,
+                       double scale, const double* shift_host, float* out, void* stream);
+
+/* Float64 mean of a cloud's rows, the same bits from run to run; stands in for the np.mean of
+ *   sample_random_trans (FCGF_APR/lib/complement_data_loader.py:33-38).  pts f32[n,3], mean f64[3] (device). */
+int apr_cloud_mean(const float* pts, int64_t n, double* mean, void* stream);
+
 /* Batched radius neighbours, sorted by distance; replaces
  *   cpp_wrappers.cpp_neighbors.radius_neighbors.batch_query(queries, supports, q_batches, s_batches, radius=)
  *   (Predator_APR/cpp_wrappers/cpp_neighbors/wrapper.cpp:71-75 -> neighbors/neighbors.cpp:211-333)
