@@ -449,7 +449,34 @@ __global__ void k_sum_bits(const unsigned* __restrict__ bits, int64_t n, double*
   if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct CropScratch {
+  unsigned* limit;   // bits of the largest squared key norm
+  uint8_t* flags;    // [n]
+  int *cnt, *off;    // [nblk] each
+};
+CropScratch walk_crop(AprArena& a, int64_t n) {
+  const size_t nblk = (size_t)cdiv64(n > 0 ? n : 1, kBlock);
+  CropScratch c;
+  c.limit = a.take<unsigned>(1);
+  c.flags = a.take<uint8_t>(n);
+  c.cnt = a.take<int>(nblk);
+  c.off = a.take<int>(nblk);
+  return c;
+}
+
+struct Nn3Scratch {
+  void* grid;           // points.hip's search grid over b: its own carve
+  int *list1, *list2;   // [n] each
+  int* counts;          // [0] list1, [1] list2
+};
+Nn3Scratch walk_nn3(AprArena& a, int64_t n, int64_t m) {
+  Nn3Scratch s;
+  s.grid = a.take<char>(apr_internal_grid_bytes(m));
+  s.list1 = a.take<int>(n);
+  s.list2 = a.take<int>(n);
+  s.counts = a.take<int>(2);
+  return s;
+}
 
 }  // namespace
 
@@ -463,24 +490,22 @@ APR_API int apr_transform_points(const float* pts, int64_t n, const float* T16_d
 }
 
 APR_API size_t apr_crop_scratch_bytes(int64_t n) {
-  const int64_t nblk = cdiv64(n > 0 ? n : 1, kBlock);
-  return align256(n) + 2 * align256(nblk * 4) + 512;
+  AprArena a(nullptr);
+  walk_crop(a, n);
+  return a.bytes();
 }
 
 APR_API int apr_crop_to_radius(const float* key_pts, int64_t n_key, const float* pts, int64_t n, float* out,
                                int32_t* n_out_dev, void* scratch, size_t scratch_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(n_key > 0 && n >= 0 && n < (1ll << 31), "apr_crop_to_radius: bad sizes");
-  APR_CHECK_ARG(scratch_bytes >= apr_crop_scratch_bytes(n), "apr_crop_to_radius: scratch too small");
-  char* p = (char*)scratch;
-  unsigned* limit = (unsigned*)p;
-  p += 256;
-  uint8_t* flags = (uint8_t*)p;
-  p += align256(n);
+  AprArena arena(scratch);
+  const CropScratch c = walk_crop(arena, n);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_crop_to_radius: scratch too small");
+  unsigned* const limit = c.limit;
+  uint8_t* const flags = c.flags;
+  int *const cnt = c.cnt, *const off = c.off;
   const int nblk = (int)cdiv64(n > 0 ? n : 1, kBlock);
-  int* cnt = (int*)p;
-  p += align256((size_t)nblk * 4);
-  int* off = (int*)p;
   APR_HIP(hipMemsetAsync(limit, 0, 4, st));
   hipLaunchKernelGGL(k_max_sqnorm, dim3(256), dim3(kBlock), 0, st, key_pts, n_key, limit);
   if (n == 0) {
@@ -514,7 +539,9 @@ APR_API int apr_chamfer_sum(const float* a, int64_t n, const float* b, int64_t m
 }
 
 APR_API size_t apr_nn3_scratch_bytes(int64_t n, int64_t m) {
-  return align256(apr_internal_grid_bytes(m)) + 2 * align256((size_t)(n > 0 ? n : 1) * 4) + 1024;
+  AprArena a(nullptr);
+  walk_nn3(a, n > 0 ? n : 1, m);
+  return a.bytes();
 }
 
 static int nn3_impl(const float* a, int64_t n, const int64_t* a_off, const float* b, int64_t m, const int64_t* b_off, int nb,
@@ -531,17 +558,12 @@ static int nn3_impl(const float* a, int64_t n, const int64_t* a_off, const float
     if (i) blen[i - 1] = (int32_t)(b_off[i] - b_off[i - 1]);
   }
   if (cell > 0.f) {
-    APR_CHECK_ARG(scratch && scratch_bytes >= apr_nn3_scratch_bytes(n, m), "apr_nn3: scratch too small");
-    char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-    void* g1s = p;
-    p += align256(apr_internal_grid_bytes(m));
-    int* list1 = (int*)p;
-    p += align256((size_t)n * 4);
-    int* list2 = (int*)p;
-    p += align256((size_t)n * 4);
-    int* counts = (int*)p;                                     // [0] list1, [1] list2
+    AprArena arena(scratch);
+    const Nn3Scratch ws = walk_nn3(arena, n, m);
+    APR_CHECK_ARG(scratch && arena.fits(scratch_bytes), "apr_nn3: scratch too small");
+    int *const list1 = ws.list1, *const list2 = ws.list2, *const counts = ws.counts;
     AprSearchGrid g1;
-    int rc = apr_internal_search_grid_batch(b, m, blen, nb, cell, g1s, &g1, st);
+    int rc = apr_internal_search_grid_batch(b, m, blen, nb, cell, ws.grid, &g1, st);
     if (rc != APR_OK) return rc;
     APR_HIP(hipMemsetAsync(counts, 0, 8, st));
     hipLaunchKernelGGL(k_nn3_grid_thread, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, a, n, b, g1, sg, best, list1, counts);

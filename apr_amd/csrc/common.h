@@ -39,6 +39,26 @@ void apr_set_error(const char* fmt, ...);
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- caller-owned scratch: every layout is ONE walk of an arena (DESIGN, "Scratch layouts") ----
+__host__ __device__ static inline size_t apr_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The walk that sizes a scratch is the walk that carves it: on nullptr take() hands out nullptr and only counts.  Every
+// region starts on a 256-byte boundary; bytes() allows for rounding an unaligned base up.  A region that another
+// translation unit carves for itself is a take<char>() of that unit's own *_bytes().
+struct AprArena {
+  char* base;      // rounded up to 256; nullptr: sizing walk
+  size_t off = 0;
+  explicit AprArena(void* scratch) : base((char*)apr_align256((size_t)scratch)) {}
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += apr_align256(count * sizeof(T));
+    return p;
+  }
+  size_t bytes() const { return off + 256; }
+  bool fits(size_t scratch_bytes) const { return scratch_bytes >= bytes(); }
+};
+
 // match.hip: brute-force NN into an initialised `best`, run only if *run_if != 0 (NULL: always)
 int apr_internal_nn_brute(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, uint64_t* best,
                           const unsigned* run_if, void* stream);

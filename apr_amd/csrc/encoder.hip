@@ -16,7 +16,6 @@
 namespace {
 
 constexpr int kLevels = 4, kStages = 7, kMaps = 10, kMaxLists = 24;
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline bool ws_shape_ok(int K, int cin, int cout) { return K <= 27 && cin % 64 == 0 && cin <= 512 && cout % 64 == 0; }
 
@@ -32,9 +31,8 @@ struct Enc {
   const apr_resunet_plan& P;
   const apr_level_map* lv;
   const int32_t* bbox;
-  bool dry;
-  char* base;
-  size_t off = 0;
+  AprArena arena;
+  const bool dry;
   hipStream_t st;
   int rc = APR_OK;
 
@@ -54,14 +52,11 @@ struct Enc {
   int ndesc = 0;
 
   Enc(const apr_resunet_plan& p, const apr_level_map* l, const int32_t* b, void* scratch, hipStream_t s)
-      : P(p), lv(l), bbox(b), dry(scratch == nullptr), base((char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255)), st(s) {}
+      : P(p), lv(l), bbox(b), arena(scratch), dry(scratch == nullptr), st(s) {}
 
-  void* take(size_t bytes) {
-    void* q = dry ? nullptr : (void*)(base + off);
-    off += al256(bytes);
-    return q;
-  }
-  float* rows(int64_t n, int c) { return (float*)take((size_t)n * c * 4); }
+  float* rows(int64_t n, int c) { return arena.take<float>((size_t)n * c); }
+  // the dry walk's total: `prod` is taken by the live walk only, at the size the dry one arrived at
+  size_t need() const { return arena.bytes() + apr_align256(prod_bytes); }
   bool ok() const { return rc == APR_OK; }
   void run(int r) {
     if (rc == APR_OK && r != APR_OK) rc = r;
@@ -84,7 +79,7 @@ struct Enc {
         size_t ints = 0;
         for (int a = 0; a < 3; ++a) ints += (size_t)lv[a].n * 27;
         ints = (ints + 63) / 64 * 64 + 64;
-        int32_t* buf = (int32_t*)take(ints * 4);
+        int32_t* buf = arena.take<int32_t>(ints);
         size_t pos = 0;
         for (int a = 0; a < 3; ++a) {
           tpool[a] = dry ? nullptr : buf + pos;
@@ -97,7 +92,7 @@ struct Enc {
       if (!dry) run(apr_kernel_map_transpose_prefilled(fwd, lv[l + 1].n, 27, lv[l].n, kmap[m], st));
       return kmap[m];
     }
-    kmap[m] = (int32_t*)take((size_t)n_out * 27 * 4);
+    kmap[m] = arena.take<int32_t>((size_t)n_out * 27);
     if (dry) return kmap[m];
     const int lin = m < 4 ? m : m - 4, lout = m < 4 ? m : m - 4 + 1;
     const apr_level_map& in = lv[lin];
@@ -134,7 +129,7 @@ struct Enc {
     s->kind = kind;
     s->rows = 0;
     s->bytes = tri ? apr_pairlist3_bytes(map_rows(m)) : apr_pairlist_bytes(map_rows(m), 27);
-    s->blob = take(s->bytes);
+    s->blob = arena.take<char>(s->bytes);
     s->built = false;
     s->counters = nullptr;
     if (!dry) {
@@ -165,7 +160,7 @@ struct Enc {
     s->kind = 2;
     s->rows = rws;
     s->bytes = apr_spconv_os_pairs_bytes(n_out, 27, rws);
-    s->blob = take(s->bytes);
+    s->blob = arena.take<char>(s->bytes);
     s->built = false;
     s->counters = nullptr;
     return s;
@@ -225,13 +220,13 @@ struct Enc {
     const int64_t n[4] = {lv[0].n, lv[1].n, lv[2].n, lv[3].n};
     // arena head: the pieces whose size does not depend on the routing
     occ_bytes = apr_occ_conv_scratch_bytes(bbox, P.conv1_ks);
-    occ = take(occ_bytes + 256);
+    occ = arena.take<char>(occ_bytes + 256);
     if (!counters) {
       n_counter_slots = 16;
-      counters = (int32_t*)take((size_t)n_counter_slots * apr_pairlist_counter_ints() * 4);
+      counters = arena.take<int32_t>((size_t)n_counter_slots * apr_pairlist_counter_ints());
       if (!dry) run(apr_fill_bytes(counters, 0, (size_t)n_counter_slots * apr_pairlist_counter_ints() * 4, st));
     }
-    if (!dry) prod = (float*)take(prod_bytes_live);
+    if (!dry) prod = (float*)arena.take<char>(prod_bytes_live);
 
     // feature rows.  Widths from the layers: CH[l] = cout of stage l's conv, TR = cout of the transposed stages
     const int ch1 = L[0].cout, ch2 = L[3].cout, ch3 = L[6].cout, ch4 = L[9].cout;
@@ -247,8 +242,8 @@ struct Enc {
       const int64_t c[kStages] = {n[0] * ch1, n[1] * ch2, n[2] * ch3, n[3] * ch4, n[2] * tr4, n[1] * tr3, n[0] * tr2};
       for (int s = 0; s < kStages; ++s) amax = c[s] > amax ? c[s] : amax;
     }
-    float* A = (float*)take((size_t)amax * 4);
-    float* H = (float*)take((size_t)amax * 4);
+    float* A = arena.take<float>((size_t)amax);
+    float* H = arena.take<float>((size_t)amax);
     float* h1 = rows(n[0], L[21].cout);
 
     struct StageIo {
@@ -324,7 +319,7 @@ APR_API size_t apr_resunet_encode_scratch_bytes(const apr_resunet_plan* plan, co
   if (!apr_resunet_encode_supported(plan, lv, bbox_host)) return 0;
   Enc e(*plan, lv, bbox_host, nullptr, nullptr);
   e.walk(nullptr, plan->layer[22].cout);
-  return e.off + al256(e.prod_bytes) + 512;
+  return e.need();
 }
 
 APR_API int apr_resunet_encode(const apr_resunet_plan* plan, const apr_level_map* lv, const int32_t* bbox_host, int32_t* counters,
@@ -336,7 +331,7 @@ APR_API int apr_resunet_encode(const apr_resunet_plan* plan, const apr_level_map
                 "apr_resunet_encode: bad arguments");
   Enc dry(*plan, lv, bbox_host, nullptr, nullptr);
   dry.walk(nullptr, ldo);
-  APR_CHECK_ARG(scratch_bytes >= dry.off + al256(dry.prod_bytes) + 512, "apr_resunet_encode: scratch too small");
+  APR_CHECK_ARG(scratch_bytes >= dry.need(), "apr_resunet_encode: scratch too small");
   Enc e(*plan, lv, bbox_host, scratch, (hipStream_t)stream);
   e.counters = counters;
   e.n_counter_slots = counters ? n_counter_slots : 0;
@@ -351,32 +346,20 @@ APR_API int apr_resunet_encode(const apr_resunet_plan* plan, const apr_level_map
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct Front {
-  bool dry;
-  char* base;
-  size_t off = 0;
-  Front(void* arena) : dry(arena == nullptr), base((char*)(((uintptr_t)arena + 255) & ~(uintptr_t)255)) {}
-  void* take(size_t bytes) {
-    void* q = dry ? nullptr : (void*)(base + off);
-    off += al256(bytes);
-    return q;
-  }
-};
-
 struct MapBufs {
   uint64_t* keys; int32_t* vals; int64_t cap; int32_t* coords; int64_t* first; int32_t *n_dev, *status; void* scratch;
   size_t scratch_bytes; int64_t rows;
 };
 
 // the builds run one behind the other on one stream: they share ONE scratch (sized for the largest, the first)
-MapBufs take_map(Front& f, int64_t rows, bool want_first, int32_t* hdr_slot, void* shared_scratch, size_t shared_bytes) {
+MapBufs take_map(AprArena& f, int64_t rows, bool want_first, int32_t* hdr_slot, void* shared_scratch, size_t shared_bytes) {
   MapBufs m;
   m.rows = rows;
   m.cap = apr_hash_capacity(rows);
-  m.keys = (uint64_t*)f.take((size_t)m.cap * 8);
-  m.vals = (int32_t*)f.take((size_t)m.cap * 4);
-  m.coords = (int32_t*)f.take((size_t)rows * 16);
-  m.first = want_first ? (int64_t*)f.take((size_t)rows * 8) : nullptr;
+  m.keys = f.take<uint64_t>((size_t)m.cap);
+  m.vals = f.take<int32_t>((size_t)m.cap);
+  m.coords = f.take<int32_t>((size_t)rows * 4);
+  m.first = want_first ? f.take<int64_t>((size_t)rows) : nullptr;
   m.scratch_bytes = shared_bytes;
   m.scratch = shared_scratch;
   m.n_dev = hdr_slot;                   // the map writes its row count and status straight into the header
@@ -388,26 +371,27 @@ MapBufs take_map(Front& f, int64_t rows, bool want_first, int32_t* hdr_slot, voi
 // larger than the voxels it ends up holding and every kernel-map probe into it would miss L2 (CoordinateManager.__init__)
 inline int64_t compact_rows_for(int64_t n_points) { return n_points > 4 * 65536 ? (n_points / 4 > 65536 ? n_points / 4 : 65536) : 0; }
 
-int front_walk(Front& f, const float* const* frames, const int64_t* offs, int32_t nseg, float vs, apr_pyramid* out,
+int front_walk(AprArena& f, const float* const* frames, const int64_t* offs, int32_t nseg, float vs, apr_pyramid* out,
                hipStream_t st) {
   const int64_t N = offs ? offs[nseg] : 0;
   const int64_t R = compact_rows_for(N);
   const int hints = 10 + nseg + 8;
-  int32_t* hdr = (int32_t*)f.take((size_t)hints * 4);
-  int32_t* counters = (int32_t*)f.take((size_t)16 * apr_pairlist_counter_ints() * 4);
-  int32_t* raw = (int32_t*)f.take((size_t)N * 16);
-  int64_t* offs_dev = (int64_t*)f.take((size_t)(nseg + 1) * 8);
-  float* pts = (float*)f.take((size_t)N * 12);
+  const bool dry = f.base == nullptr;
+  int32_t* hdr = f.take<int32_t>((size_t)hints);
+  int32_t* counters = f.take<int32_t>((size_t)16 * apr_pairlist_counter_ints());
+  int32_t* raw = f.take<int32_t>((size_t)N * 4);
+  int64_t* offs_dev = f.take<int64_t>((size_t)(nseg + 1));
+  float* pts = f.take<float>((size_t)N * 3);
   // level 0 = the compact table if there is one, else the de-duplicating table itself
   const size_t sbytes = apr_map_scratch_bytes(N);
-  void* const sc = f.take(sbytes);
-  MapBufs dedup = take_map(f, N, true, f.dry ? nullptr : hdr + (R ? 8 : 0), sc, sbytes);
+  void* const sc = f.take<char>(sbytes);
+  MapBufs dedup = take_map(f, N, true, dry ? nullptr : hdr + (R ? 8 : 0), sc, sbytes);
   MapBufs lvl[4];
-  if (R) lvl[0] = take_map(f, R, false, f.dry ? nullptr : hdr, sc, sbytes);
+  if (R) lvl[0] = take_map(f, R, false, dry ? nullptr : hdr, sc, sbytes);
   else lvl[0] = dedup;
   const int64_t rows = R ? R : N;
-  for (int l = 1; l < 4; ++l) lvl[l] = take_map(f, rows, false, f.dry ? nullptr : hdr + 2 * l, sc, sbytes);
-  if (f.dry) return APR_OK;
+  for (int l = 1; l < 4; ++l) lvl[l] = take_map(f, rows, false, dry ? nullptr : hdr + 2 * l, sc, sbytes);
+  if (dry) return APR_OK;
 
   int rc;
   // the header and the pair-list counters behind it (adjacent in the arena) cleared by one small launch (k_pack_i32's
@@ -449,11 +433,11 @@ int front_walk(Front& f, const float* const* frames, const int64_t* offs, int32_
 
 APR_API size_t apr_voxel_pyramid_scratch_bytes(int64_t n_points, int32_t nseg) {
   if (n_points <= 0 || nseg <= 0 || nseg > APR_MAX_FRAMES) return 0;
-  Front f(nullptr);
+  AprArena f(nullptr);
   int64_t offs[APR_MAX_FRAMES + 1] = {};
   offs[nseg] = n_points;
   (void)front_walk(f, nullptr, offs, nseg, 1.f, nullptr, nullptr);
-  return f.off + 512;
+  return f.bytes();
 }
 
 APR_API int apr_voxel_pyramid(const float* const* frames_host, const int64_t* offsets_host, int32_t nseg, float voxel_size,
@@ -462,6 +446,6 @@ APR_API int apr_voxel_pyramid(const float* const* frames_host, const int64_t* of
                 "apr_voxel_pyramid: bad arguments (1 .. %d frames)", APR_MAX_FRAMES);
   APR_CHECK_ARG(offsets_host[0] == 0 && offsets_host[nseg] > 0, "apr_voxel_pyramid: offsets must run 0 .. total points > 0");
   APR_CHECK_ARG(arena_bytes >= apr_voxel_pyramid_scratch_bytes(offsets_host[nseg], nseg), "apr_voxel_pyramid: arena too small");
-  Front f(arena);
+  AprArena f(arena);
   return front_walk(f, frames_host, offsets_host, nseg, voxel_size, out, (hipStream_t)stream);
 }

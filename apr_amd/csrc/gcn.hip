@@ -10,13 +10,9 @@
 #include "common.h"
 
 namespace {
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Gcn {
   const apr_gcn_desc& D;
-  bool dry;
-  char* base;
-  size_t off = 0;
+  AprArena arena;
   hipStream_t st;
   int rc = APR_OK;
   // shared by the two clouds (one stream: they run one behind the other)
@@ -28,12 +24,7 @@ struct Gcn {
   float* nxt[2];
 
   Gcn(const apr_gcn_desc& d, void* scratch, hipStream_t s)
-      : D(d), dry(scratch == nullptr), base((char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255)), st(s) {}
-  void* take(size_t bytes) {
-    void* p = dry ? nullptr : (void*)(base + off);
-    off += al256(bytes);
-    return p;
-  }
+      : D(d), arena(scratch), st(s) {}
   void run(int r) {
     if (rc == APR_OK && r != APR_OK) rc = r;
   }
@@ -46,26 +37,26 @@ struct Gcn {
     for (int i = 0; i < D.n_layers; ++i)
       if (D.layer[i].kind == 0 && D.layer[i].k > kmax) kmax = D.layer[i].k;
     const int64_t nk = n * kmax;
-    knn = (int32_t*)take((size_t)nk * 4);
-    e = (float*)take((size_t)nk * 2 * c * 4);
-    y = (float*)take((size_t)nk * 2 * c * 4);
-    ss = (float*)take((size_t)4 * c * 4);
-    cat4 = (float*)take((size_t)n * 4 * c * 4);
-    x3 = (float*)take((size_t)n * c * 4);
-    q = (float*)take((size_t)n * c * 4);
-    k = (float*)take((size_t)n * c * 4);
-    v = (float*)take((size_t)n * c * 4);
-    att = (float*)take((size_t)n * c * 4);
-    cat2 = (float*)take((size_t)n * 2 * c * 4);
-    h = (float*)take((size_t)n * 2 * c * 4);
-    h2 = (float*)take((size_t)n * 2 * c * 4);
-    delta = (float*)take((size_t)n * c * 4);
+    knn = arena.take<int32_t>((size_t)nk);
+    e = arena.take<float>((size_t)nk * 2 * c);
+    y = arena.take<float>((size_t)nk * 2 * c);
+    ss = arena.take<float>((size_t)4 * c);
+    cat4 = arena.take<float>((size_t)n * 4 * c);
+    x3 = arena.take<float>((size_t)n * c);
+    q = arena.take<float>((size_t)n * c);
+    k = arena.take<float>((size_t)n * c);
+    v = arena.take<float>((size_t)n * c);
+    att = arena.take<float>((size_t)n * c);
+    cat2 = arena.take<float>((size_t)n * 2 * c);
+    h = arena.take<float>((size_t)n * 2 * c);
+    h2 = arena.take<float>((size_t)n * 2 * c);
+    delta = arena.take<float>((size_t)n * c);
     stat_bytes = apr_bn_stats_scratch_bytes(nk > n ? nk : n, 2 * c);
-    stat = take(stat_bytes);
-    cur[0] = (float*)take((size_t)n0 * c * 4);
-    cur[1] = (float*)take((size_t)n1 * c * 4);
-    nxt[0] = (float*)take((size_t)n0 * c * 4);
-    nxt[1] = (float*)take((size_t)n1 * c * 4);
+    stat = arena.take<char>(stat_bytes);
+    cur[0] = arena.take<float>((size_t)n0 * c);
+    cur[1] = arena.take<float>((size_t)n1 * c);
+    nxt[0] = arena.take<float>((size_t)n0 * c);
+    nxt[1] = arena.take<float>((size_t)n1 * c);
   }
 
   int gemm(const float* in, int64_t ldi, int64_t m, int cin, int cout, const void* w, const float* shift, float* out, int64_t ldo) {
@@ -129,7 +120,7 @@ APR_API size_t apr_gcn_scratch_bytes(const apr_gcn_desc* d, int32_t n0, int32_t 
   if (!gcn_ok(d, n0, n1)) return 0;
   Gcn g(*d, nullptr, nullptr);
   g.carve(n0, n1);
-  return g.off + 512;
+  return g.arena.bytes();
 }
 
 APR_API int apr_gcn_forward(const apr_gcn_desc* d, const float* pts0, int32_t n0, const float* pts1, int32_t n1, const float* x0,
@@ -138,11 +129,11 @@ APR_API int apr_gcn_forward(const apr_gcn_desc* d, const float* pts0, int32_t n0
   APR_CHECK_ARG(gcn_ok(d, n0, n1), "apr_gcn_forward: descriptor / sizes not covered (c %% 64 == 0, 64 channels per head, k < n)");
   APR_CHECK_ARG(pts0 && pts1 && x0 && x1 && out0 && out1 && scratch && ldx0 >= d->c && ldx1 >= d->c && ldo0 >= d->c && ldo1 >= d->c,
                 "apr_gcn_forward: bad arguments");
-  APR_CHECK_ARG(scratch_bytes >= apr_gcn_scratch_bytes(d, n0, n1), "apr_gcn_forward: scratch too small");
   APR_CHECK_ARG(ldx0 % 4 == 0 && ldx1 % 4 == 0 && ((uintptr_t)x0 | (uintptr_t)x1) % 16 == 0,
                 "apr_gcn_forward: the descriptors must be 16-byte aligned rows");
   Gcn g(*d, scratch, (hipStream_t)stream);
   g.carve(n0, n1);
+  APR_CHECK_ARG(g.arena.fits(scratch_bytes), "apr_gcn_forward: scratch too small");
   const float* in[2] = {x0, x1};
   int64_t ldi[2] = {ldx0, ldx1};
   const float* pts[2] = {pts0, pts1};

@@ -343,11 +343,27 @@ APR_API int64_t apr_hash_capacity(int64_t n) {
   return cap;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+namespace {
+struct MapScratch {
+  int* slot_of;      // [n]
+  uint8_t* flags;    // [n]
+  int *blk_cnt, *blk_off;   // [nblk] each
+};
+MapScratch walk_map(AprArena& a, int64_t n) {
+  const size_t nblk = (size_t)cdiv64(n > 0 ? n : 1, kBlock);
+  MapScratch m;
+  m.slot_of = a.take<int>(n);
+  m.flags = a.take<uint8_t>(n);
+  m.blk_cnt = a.take<int>(nblk);
+  m.blk_off = a.take<int>(nblk);
+  return m;
+}
+}  // namespace
 
 APR_API size_t apr_map_scratch_bytes(int64_t n) {
-  int64_t nblk = cdiv64(n > 0 ? n : 1, kBlock);
-  return align256(n * 4) + align256(n) + 2 * align256(nblk * 4) + 256;
+  AprArena a(nullptr);
+  walk_map(a, n);
+  return a.bytes();
 }
 
 APR_API int apr_voxelize(const float* xyz, int64_t n, float voxel_size, int32_t batch,
@@ -370,7 +386,9 @@ APR_API int apr_map_build(const int32_t* coords_in, int64_t n, const int32_t* n_
   APR_CHECK_ARG(n >= 0 && n < (1ll << 31), "apr_map_build: n=%lld out of range", (long long)n);
   APR_CHECK_ARG(cap >= 2 * n && (cap & (cap - 1)) == 0, "apr_map_build: cap=%lld must be a power of two >= 2n",
                 (long long)cap);
-  APR_CHECK_ARG(scratch_bytes >= apr_map_scratch_bytes(n), "apr_map_build: scratch too small");
+  AprArena arena(scratch);
+  const MapScratch m = walk_map(arena, n);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_map_build: scratch too small");
   APR_CHECK_ARG(floor_to >= 0, "apr_map_build: floor_to < 0");
   hipLaunchKernelGGL(k_table_init, dim3((unsigned)cdiv64(cap, 256)), dim3(256), 0, st, (unsigned long long*)keys, vals,
                      cap, status, n == 0 ? n_out : (int*)nullptr);
@@ -379,21 +397,13 @@ APR_API int apr_map_build(const int32_t* coords_in, int64_t n, const int32_t* n_
     return APR_OK;
   }
   const int nblk = (int)cdiv64(n, kBlock);
-  char* p = (char*)scratch;
-  int* slot_of = (int*)p;
-  p += align256(n * 4);
-  uint8_t* flags = (uint8_t*)p;
-  p += align256(n);
-  int* blk_cnt = (int*)p;
-  p += align256((size_t)nblk * 4);
-  int* blk_off = (int*)p;
   const uint32_t mask = (uint32_t)(cap - 1);
   hipLaunchKernelGGL(k_insert, dim3(nblk), dim3(kBlock), 0, st, (const int4*)coords_in, n, n_dev,
-                     floor_to, (unsigned long long*)keys, vals, mask, slot_of, status);
-  hipLaunchKernelGGL(k_flag_count, dim3(nblk), dim3(kBlock), 0, st, vals, slot_of, n, n_dev, flags, blk_cnt);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, blk_cnt, nblk, blk_off, n_out);
+                     floor_to, (unsigned long long*)keys, vals, mask, m.slot_of, status);
+  hipLaunchKernelGGL(k_flag_count, dim3(nblk), dim3(kBlock), 0, st, vals, m.slot_of, n, n_dev, m.flags, m.blk_cnt);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, m.blk_cnt, nblk, m.blk_off, n_out);
   hipLaunchKernelGGL(k_compact, dim3(nblk), dim3(kBlock), 0, st, (const int4*)coords_in, n, n_dev, floor_to,
-                     flags, blk_off, slot_of, vals, (int4*)out_coords, (long long*)out_first);
+                     m.flags, m.blk_off, m.slot_of, vals, (int4*)out_coords, (long long*)out_first);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }

@@ -26,7 +26,6 @@ constexpr int kIcpBlock = 256;
 constexpr int kIcpSums = 17;          // count, p[3], q[3], p q^T [9], d^2
 constexpr int kIcpChunk = 8;          // rounds enqueued between two looks at the flags
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct IcpBatch {
   int nb;
@@ -265,18 +264,13 @@ struct IcpScratch {
   int* done;
 };
 
-static size_t icp_carve(void* scratch, int64_t n, int64_t m, int nb, IcpScratch* out) {
-  char* p0 = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  char* p = p0;
-  out->grid = p;
-  p += align256(apr_internal_grid_bytes(m));
-  out->rows = (float4*)p;
-  p += align256((size_t)(m > 0 ? m : 1) * 16);
-  out->partial = (double*)p;
-  p += align256((size_t)icp_total_blocks(n > 0 ? n : 1, nb) * kIcpSums * 8);
-  out->done = (int*)p;
-  p += align256((size_t)kIcpMaxProblems * 4);
-  return (size_t)(p - p0) + 256;
+static IcpScratch icp_walk(AprArena& a, int64_t n, int64_t m, int nb) {
+  IcpScratch s;
+  s.grid = a.take<char>(apr_internal_grid_bytes(m));      // points.hip's search grid: its own carve
+  s.rows = a.take<float4>(m > 0 ? m : 1);
+  s.partial = a.take<double>((size_t)icp_total_blocks(n > 0 ? n : 1, nb) * kIcpSums);
+  s.done = a.take<int>(kIcpMaxProblems);
+  return s;
 }
 
 }  // namespace
@@ -288,8 +282,9 @@ int apr_internal_icp_pack(const float* tgt, int64_t m, AprSearchGrid g, float4* 
 }
 
 APR_API size_t apr_icp_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb) {
-  IcpScratch s;
-  return icp_carve(nullptr, n_src_total, n_tgt_total, nb > 0 ? nb : 1, &s);
+  AprArena a(nullptr);
+  icp_walk(a, n_src_total, n_tgt_total, nb > 0 ? nb : 1);
+  return a.bytes();
 }
 
 APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, const float* tgt, const int64_t* tgt_offsets_host,
@@ -311,7 +306,9 @@ APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, con
     APR_CHECK_ARG(tgt_offsets_host[i + 1] > tgt_offsets_host[i], "apr_icp_batch: empty target segment %d", i);
   const int64_t n = src_offsets_host[nb], m = tgt_offsets_host[n_tgt];
   APR_CHECK_ARG(n < (1ll << 31) - kIcpBlock * (kIcpMaxProblems + 1) && m < (1ll << 31) - 1, "apr_icp_batch: oversized clouds");
-  APR_CHECK_ARG(scratch && scratch_bytes >= apr_icp_scratch_bytes(n, m, nb), "apr_icp_batch: scratch too small");
+  AprArena arena(scratch);
+  const IcpScratch w = icp_walk(arena, n, m, nb);
+  APR_CHECK_ARG(scratch && arena.fits(scratch_bytes), "apr_icp_batch: scratch too small");
   IcpBatch sg;
   sg.nb = nb;
   sg.blk0[0] = 0;
@@ -329,8 +326,6 @@ APR_API int apr_icp_batch(const float* src, const int64_t* src_offsets_host, con
     if (i) tlen[i - 1] = (int32_t)(tgt_offsets_host[i] - tgt_offsets_host[i - 1]);
   }
   const int nblk = sg.blk0[nb];
-  IcpScratch w;
-  icp_carve(scratch, n, m, nb, &w);
 
   const float rf = (float)max_dist;
   const float r2 = rf * rf;                      // the strict bound, in the precision of d^2

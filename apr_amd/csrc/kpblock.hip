@@ -10,38 +10,28 @@
 #include "common.h"
 
 namespace {
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct KpCarve {
   float *u1, *rs, *wf, *kp, *pool, *sc, *y;
   void* stat;
-  size_t stat_bytes, total;
+  size_t stat_bytes;
 };
 
-KpCarve kp_carve(const apr_kp_resnet_desc& d, void* scratch) {
+KpCarve kp_walk(AprArena& a, const apr_kp_resnet_desc& d) {
   KpCarve c;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  char* const p0 = p;
-  auto take = [&](size_t bytes) {
-    char* q = p;
-    p += al256(bytes);
-    return q;
-  };
   const int64_t ni = d.n_in, no = d.n_out;
-  c.u1 = d.w_unary1 ? (float*)take((size_t)ni * d.mid * 4) : nullptr;
-  c.rs = (float*)take((size_t)ni * 4);
-  c.wf = (float*)take((size_t)no * d.n_kp * d.mid * 4);
-  c.kp = (float*)take((size_t)no * d.mid * 4);
-  c.pool = d.strided ? (float*)take((size_t)no * d.in_dim * 4) : nullptr;
-  c.sc = d.w_shortcut ? (float*)take((size_t)no * d.out_dim * 4) : nullptr;
-  c.y = (float*)take((size_t)no * d.out_dim * 4);
+  c.u1 = d.w_unary1 ? a.take<float>((size_t)ni * d.mid) : nullptr;
+  c.rs = a.take<float>((size_t)ni);
+  c.wf = a.take<float>((size_t)no * d.n_kp * d.mid);
+  c.kp = a.take<float>((size_t)no * d.mid);
+  c.pool = d.strided ? a.take<float>((size_t)no * d.in_dim) : nullptr;
+  c.sc = d.w_shortcut ? a.take<float>((size_t)no * d.out_dim) : nullptr;
+  c.y = a.take<float>((size_t)no * d.out_dim);
   const int64_t nmax = ni > no ? ni : no;
   const int32_t cmax = d.out_dim > d.in_dim ? d.out_dim : d.in_dim;
   c.stat_bytes = apr_bn_stats_scratch_bytes(nmax + 256 * (int64_t)(d.nseg > 0 ? d.nseg : 1), cmax);
   const size_t fused = apr_dense_gemm_bf3_norm_scratch_bytes(nmax, cmax, d.nseg > 0 ? d.nseg : 1);
   if (fused > c.stat_bytes) c.stat_bytes = fused;
-  c.stat = take(c.stat_bytes);
-  c.total = (size_t)(p - p0) + 256;
+  c.stat = a.take<char>(c.stat_bytes);
   return c;
 }
 
@@ -71,7 +61,9 @@ int kp_linear_norm(const apr_kp_resnet_desc& d, const KpCarve& c, const float* x
 
 APR_API size_t apr_kp_resnet_scratch_bytes(const apr_kp_resnet_desc* d) {
   if (!d || d->n_in <= 0 || d->n_out <= 0 || d->mid <= 0 || d->in_dim <= 0 || d->out_dim <= 0 || d->n_kp <= 0) return 0;
-  return kp_carve(*d, nullptr).total;
+  AprArena a(nullptr);
+  kp_walk(a, *d);
+  return a.bytes();
 }
 
 APR_API int apr_kp_resnet_block(const apr_kp_resnet_desc* dp, void* stream) {
@@ -86,8 +78,9 @@ APR_API int apr_kp_resnet_block(const apr_kp_resnet_desc* dp, void* stream) {
   APR_CHECK_ARG((d.w_shortcut != nullptr) == (d.in_dim != d.out_dim), "apr_kp_resnet_block: shortcut Linear exists iff in_dim != out_dim");
   APR_CHECK_ARG(d.strided || d.n_in == d.n_out, "apr_kp_resnet_block: a same-level block maps n_in rows to n_in rows");
   APR_CHECK_ARG(d.nseg <= 1 || (d.seg_in && d.seg_out), "apr_kp_resnet_block: segment offsets missing");
-  const KpCarve c = kp_carve(d, d.scratch);
-  APR_CHECK_ARG(d.scratch_bytes >= c.total, "apr_kp_resnet_block: scratch too small");
+  AprArena arena(d.scratch);
+  const KpCarve c = kp_walk(arena, d);
+  APR_CHECK_ARG(arena.fits(d.scratch_bytes), "apr_kp_resnet_block: scratch too small");
   int rc;
 #define KP_TRY(call)            \
   do {                          \

@@ -575,8 +575,6 @@ __global__ __launch_bounds__(256) void k_nn_resolve(const unsigned long long* __
   }
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int64_t shared_capacity(int64_t n0) {   // shared overflow list: 64 candidates per query
   int64_t c = 64 * n0;
   if (c < 65536) c = 65536;
@@ -607,29 +605,32 @@ void nn_grid(int64_t n0, int64_t n1, int feat_c, int64_t* qblocks, int64_t* chun
 size_t dense_list_bytes(int64_t qblocks, int64_t nchunk, int64_t chunk) {
   uint64_t nflag = (uint64_t)(qblocks * 4) * (uint64_t)nchunk * (uint64_t)(chunk / 16);
   if (nflag > kDenseListCap) nflag = kDenseListCap;
-  return al256((size_t)nflag * 4 + 64);
+  return apr_align256((size_t)nflag * 4 + 64);
 }
 
 template <int C>
-int run_fast(const float* f0, int64_t n0, const float* f1, int64_t n1, unsigned long long* best, char* p,
-             hipStream_t st) {
+int run_fast(const float* f0, int64_t n0, const float* f1, int64_t n1, unsigned long long* best, void* scratch,
+             size_t scratch_bytes, hipStream_t st) {
+  AprArena a(scratch);
   int64_t qblocks, chunk, nchunk;
   nn_grid(n0, n1, C, &qblocks, &chunk, &nchunk);
   const int64_t nwaves = qblocks * nchunk * 4;
-  unsigned short* qb = (unsigned short*)p;  p += al256((size_t)n0 * C * 2);
-  unsigned short* ql = (unsigned short*)p;  p += al256((size_t)n0 * C * 2);
-  unsigned short* tb = (unsigned short*)p;  p += al256((size_t)n1 * C * 2);
-  unsigned short* tl = (unsigned short*)p;  p += al256((size_t)n1 * C * 2);
-  f32x4* qmeta = (f32x4*)p;                 p += al256((size_t)n0 * 16);
-  f32x4* tmeta = (f32x4*)p;                 p += al256((size_t)n1 * 16);
-  unsigned* U = (unsigned*)p;               p += al256((size_t)n0 * 4);
-  unsigned* overflow = (unsigned*)p;        p += 256;
-  unsigned* cand_count = (unsigned*)p;      p += al256((size_t)nwaves * 4);
-  unsigned long long* cand = (unsigned long long*)p;   p += al256((size_t)nwaves * kCandWave * 8);
-  unsigned long long* shared_list = (unsigned long long*)p;   p += al256((size_t)shared_capacity(n0) * 8);
+  unsigned short* qb = a.take<unsigned short>((size_t)n0 * C);
+  unsigned short* ql = a.take<unsigned short>((size_t)n0 * C);
+  unsigned short* tb = a.take<unsigned short>((size_t)n1 * C);
+  unsigned short* tl = a.take<unsigned short>((size_t)n1 * C);
+  f32x4* qmeta = a.take<f32x4>(n0);
+  f32x4* tmeta = a.take<f32x4>(n1);
+  unsigned* U = a.take<unsigned>(n0);
+  unsigned* overflow = a.take<unsigned>(64);
+  unsigned* cand_count = a.take<unsigned>(nwaves);
+  unsigned long long* cand = a.take<unsigned long long>((size_t)nwaves * kCandWave);
+  unsigned long long* shared_list = a.take<unsigned long long>(shared_capacity(n0));
   // (the flag bytes of earlier rounds sat here; the scratch bound still counts them)
-  p += al256((size_t)(qblocks * 4) * (size_t)nchunk * (size_t)(chunk / 16) + 64);
-  unsigned* dense_list = (unsigned*)p;                        // ids of the dense blocks, appended by the refine pass
+  a.take<char>((size_t)(qblocks * 4) * (size_t)nchunk * (size_t)(chunk / 16) + 64);
+  // ids of the dense blocks, appended by the refine pass
+  unsigned* dense_list = (unsigned*)a.take<char>(dense_list_bytes(qblocks, nchunk, chunk));
+  APR_CHECK_ARG(a.fits(scratch_bytes), "apr_feature_nn_fast: scratch too small");
   const unsigned shared_cap = (unsigned)shared_capacity(n0);
   constexpr int LPR = C / 4;
   if ((uint64_t)qblocks * 4 * (uint64_t)nchunk * (uint64_t)(chunk / 16) + 64 >= (1ull << 32)) {
@@ -669,9 +670,10 @@ APR_API size_t apr_feature_nn_fast_scratch_bytes(int64_t n0, int64_t n1, int32_t
   const size_t nwaves = 4 * (768 + qblocks);
   const size_t nflag = qblocks * 4 * ((2 * (size_t)n1 + 320) / 16 + 1);
   const size_t nlist = nflag > kDenseListCap ? (size_t)kDenseListCap : nflag;
-  return 2 * al256((size_t)n0 * c * 2) + 2 * al256((size_t)n1 * c * 2) + al256((size_t)n0 * 16) + al256((size_t)n1 * 16) +
-         al256((size_t)n0 * 4) + 256 + al256(nwaves * 4) + al256(nwaves * kCandWave * 8) +
-         al256((size_t)shared_capacity(n0) * 8) + al256(nflag + 64) + al256(nlist * 4 + 64) + 512;
+  const auto al = apr_align256;
+  return 2 * al((size_t)n0 * c * 2) + 2 * al((size_t)n1 * c * 2) + al((size_t)n0 * 16) + al((size_t)n1 * 16) +
+         al((size_t)n0 * 4) + 256 + al(nwaves * 4) + al(nwaves * kCandWave * 8) +
+         al((size_t)shared_capacity(n0) * 8) + al(nflag + 64) + al(nlist * 4 + 64) + 512;
 }
 
 APR_API int apr_feature_nn_fast(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, uint64_t* best,
@@ -685,9 +687,8 @@ APR_API int apr_feature_nn_fast(const float* f0, int64_t n0, const float* f1, in
   APR_CHECK_ARG(((((uintptr_t)f0) | ((uintptr_t)f1)) & 15) == 0, "apr_feature_nn_fast: 16-byte aligned rows required");
   APR_CHECK_ARG(scratch_bytes >= apr_feature_nn_fast_scratch_bytes(n0, n1, c), "apr_feature_nn_fast: scratch too small");
   if (n0 == 0) return APR_OK;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
   unsigned long long* b = (unsigned long long*)best;
-  if (c == 32) return run_fast<32>(f0, n0, f1, n1, b, p, st);
-  if (c == 64) return run_fast<64>(f0, n0, f1, n1, b, p, st);
-  return run_fast<128>(f0, n0, f1, n1, b, p, st);
+  if (c == 32) return run_fast<32>(f0, n0, f1, n1, b, scratch, scratch_bytes, st);
+  if (c == 64) return run_fast<64>(f0, n0, f1, n1, b, scratch, scratch_bytes, st);
+  return run_fast<128>(f0, n0, f1, n1, b, scratch, scratch_bytes, st);
 }

@@ -26,7 +26,6 @@ constexpr int kBlock = 256;
 constexpr int kMaxBatch = 64;
 constexpr int kHitCap = 1024;  // max neighbours per query the radius kernels can rank
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- per-cloud bounding-box minimum -------------------------------------------------------
 constexpr int kMinThreads = 1024;   // one workgroup per cloud: 1024 threads x 4 independent points in flight
@@ -705,39 +704,32 @@ struct GridWork {
   int* big;   // [0]: number of cells with more than kCellCap points; their ids are listed in `cnt` (dead after the scan)
 };
 
-size_t grid_work_bytes(int64_t n) {
-  const int64_t cap = apr_hash_capacity(n);
-  return align256(n * 16) + align256(cap * 8) + align256(cap * 4) + align256(n * 16) + 256 + 256 + align256(n * 4) +
-         align256(n * 4) + align256((n + 1) * 4) + align256(n * 4) + align256(n * 4) +
-         align256(apr_map_scratch_bytes(n)) + align256((kMaxBatch + 1) * 4) + align256(kMaxBatch * 12) + 1024;
-}
-
-GridWork carve(void* scratch, int64_t n) {
+// The one layout of a grid build: the sizing walk (nullptr arena) and every carve of the same scratch, apr_internal_buckets_begin
+// and _finish included, go through here and so agree.
+GridWork walk_grid(AprArena& a, int64_t n) {
   GridWork w;
-  char* p = (char*)scratch;
   w.cap = apr_hash_capacity(n);
-  auto take = [&](size_t bytes) {
-    void* r = p;
-    p += align256(bytes);
-    return r;
-  };
-  w.coords = (int4*)take(n * 16);
-  w.keys = (unsigned long long*)take(w.cap * 8);
-  w.vals = (int*)take(w.cap * 4);
-  w.cell_coords = (int4*)take(n * 16);
-  w.n_cells = (int*)take(256);
-  w.status = (int*)take(256);
-  w.cell = (int*)take(n * 4);
-  w.cnt = (int*)take(n * 4);
-  w.start = (int*)take((n + 1) * 4);
-  w.cursor = (int*)take(n * 4);
-  w.sorted = (int*)take(n * 4);
+  w.coords = a.take<int4>(n);
+  w.keys = a.take<unsigned long long>(w.cap);
+  w.vals = a.take<int>(w.cap);
+  w.cell_coords = a.take<int4>(n);
+  w.n_cells = a.take<int>(1);
+  w.status = a.take<int>(1);
+  w.cell = a.take<int>(n);
+  w.cnt = a.take<int>(n);
+  w.start = a.take<int>(n + 1);
+  w.cursor = a.take<int>(n);
+  w.sorted = a.take<int>(n);
   w.map_scratch_bytes = apr_map_scratch_bytes(n);
-  w.map_scratch = take(w.map_scratch_bytes);
-  w.starts_dev = (int*)take((kMaxBatch + 1) * 4);
-  w.mins = (float*)take(kMaxBatch * 12);
-  w.big = (int*)take(256);
+  w.map_scratch = a.take<char>(w.map_scratch_bytes);
+  w.starts_dev = a.take<int>(kMaxBatch + 1);
+  w.mins = a.take<float>(kMaxBatch * 3);
+  w.big = a.take<int>(1);
   return w;
+}
+GridWork carve(void* scratch, int64_t n) {
+  AprArena a(scratch);
+  return walk_grid(a, n);
 }
 
 // Batch start offsets reach the device as a kernel argument, not by hipMemcpyAsync from a stack array: the
@@ -782,16 +774,17 @@ int build_grid(const float* pts, int64_t n, const int32_t* lengths_host, int nb,
 
 }  // namespace
 
-APR_API size_t apr_grid_subsample_scratch_bytes(int64_t n) { return grid_work_bytes(n > 0 ? n : 1); }
+APR_API size_t apr_grid_subsample_scratch_bytes(int64_t n) { return apr_internal_grid_bytes(n); }
 
 namespace {
 int grid_subsample_enqueue(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, float dl,
                            const float* feats, int32_t fdim, float* out_pts, float* out_feats, void* scratch,
                            size_t scratch_bytes, GridWork* w_out, hipStream_t st) {
   APR_CHECK_ARG(n > 0 && n < (1ll << 31) && nb > 0 && nb <= kMaxBatch && dl > 0.f, "apr_grid_subsample: bad arguments");
-  APR_CHECK_ARG(scratch_bytes >= grid_work_bytes(n), "apr_grid_subsample: scratch too small");
+  AprArena arena(scratch);
+  GridWork w = walk_grid(arena, n);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_grid_subsample: scratch too small");
   for (int b = 0; b < nb; ++b) APR_CHECK_ARG(lengths_host[b] > 0, "apr_grid_subsample: empty cloud in batch");
-  GridWork w = carve(scratch, n);
   int rc = build_grid(pts, n, lengths_host, nb, dl, 0, w, st);
   if (rc != APR_OK) return rc;
   int* out_len_dev = w.cursor;  // cursor is dead after k_fill; reuse its first nb ints
@@ -844,24 +837,15 @@ APR_API int apr_grid_subsample_async(const float* pts, int64_t n, const int32_t*
 
 // internal (not part of the C ABI): uniform search grid over one cloud, used by the geometric
 // RANSAC validation in ransac.hip
-size_t apr_internal_grid_bytes(int64_t n) { return grid_work_bytes(n > 0 ? n : 1); }
+size_t apr_internal_grid_bytes(int64_t n) {
+  AprArena a(nullptr);
+  walk_grid(a, n > 0 ? n : 1);
+  return a.bytes();
+}
 int apr_internal_search_grid(const float* pts, int64_t n, float cell, void* scratch, AprSearchGrid* out,
                              hipStream_t st) {
-  GridWork w = carve(scratch, n);
-  int32_t len = (int32_t)n;
-  int rc = build_grid(pts, n, &len, 1, cell, 1, w, st);
-  if (rc != APR_OK) return rc;
-  out->keys = w.keys;
-  out->vals = w.vals;
-  out->mask = (uint32_t)(w.cap - 1);
-  out->start = w.start;
-  out->sorted = w.sorted;
-  out->mins = w.mins;
-  out->cell = cell;
-  out->cell_coords = w.cell_coords;
-  out->n_cells = w.n_cells;
-  out->status = w.status;
-  return APR_OK;
+  const int32_t len = (int32_t)n;
+  return apr_internal_search_grid_batch(pts, n, &len, 1, cell, scratch, out, st);
 }
 
 // the same over a BATCH of clouds stacked in pts (lengths_host[nb]): cells are keyed (cloud, x, y, z), origins per cloud
@@ -933,8 +917,27 @@ int apr_internal_buckets_finish(int64_t n, void* scratch, int64_t* first, hipStr
   return APR_OK;
 }
 
+namespace {
+struct RadiusWork {
+  GridWork w;     // first, where apr_radius_neighbors_regrid_async finds the previous call's grid
+  int* counts;    // [nq]
+  int* qstarts;   // [kMaxBatch + 1]
+  int* maxc;
+};
+RadiusWork walk_radius(AprArena& a, int64_t nq, int64_t ns) {
+  RadiusWork r;
+  r.w = walk_grid(a, ns);
+  r.counts = a.take<int>(nq);
+  r.qstarts = a.take<int>(kMaxBatch + 1);
+  r.maxc = a.take<int>(1);
+  return r;
+}
+}  // namespace
+
 APR_API size_t apr_radius_scratch_bytes(int64_t nq, int64_t ns) {
-  return grid_work_bytes(ns > 0 ? ns : 1) + align256((nq > 0 ? nq : 1) * 4) + align256((kMaxBatch + 1) * 4) + 512;
+  AprArena a(nullptr);
+  walk_radius(a, nq > 0 ? nq : 1, ns > 0 ? ns : 1);
+  return a.bytes();
 }
 
 APR_API int apr_radius_neighbors(const float* queries, int64_t nq, const float* supports, int64_t ns,
@@ -944,14 +947,11 @@ APR_API int apr_radius_neighbors(const float* queries, int64_t nq, const float* 
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(nq > 0 && ns > 0 && nq < (1ll << 31) && ns < (1ll << 31) && nb > 0 && nb <= kMaxBatch && radius > 0.f,
                 "apr_radius_neighbors: bad arguments");
-  APR_CHECK_ARG(scratch_bytes >= apr_radius_scratch_bytes(nq, ns), "apr_radius_neighbors: scratch too small");
-  GridWork w = carve(scratch, ns);
-  char* p = (char*)scratch + grid_work_bytes(ns);
-  int* counts = (int*)p;
-  p += align256(nq * 4);
-  int* qstarts = (int*)p;
-  p += align256((kMaxBatch + 1) * 4);
-  int* maxc = (int*)p;
+  AprArena arena(scratch);
+  const RadiusWork rw = walk_radius(arena, nq, ns);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_radius_neighbors: scratch too small");
+  GridWork w = rw.w;
+  int *const counts = rw.counts, *const qstarts = rw.qstarts, *const maxc = rw.maxc;
   const float cell = 1.01f * radius;   // as icp.hip: the 1 % covers the cell index's fp32 roundings (common.h)
   int rc = build_grid(supports, ns, s_lengths_host, nb, cell, 1, w, st);
   if (rc != APR_OK) return rc;
@@ -1014,12 +1014,11 @@ static int radius_async(const float* queries, int64_t nq, const float* supports,
                 "apr_radius_neighbors_async: bad arguments");
   APR_CHECK_ARG(limit > 0 && out != nullptr && out_ld >= limit && flags_dev != nullptr,
                 "apr_radius_neighbors_async: needs limit > 0, an output of >= limit columns and the flag words");
-  APR_CHECK_ARG(scratch_bytes >= apr_radius_scratch_bytes(nq, ns), "apr_radius_neighbors_async: scratch too small");
-  GridWork w = carve(scratch, ns);
-  char* p = (char*)scratch + grid_work_bytes(ns);
-  int* counts = (int*)p;
-  p += align256(nq * 4);
-  int* qstarts = (int*)p;
+  AprArena arena(scratch);
+  const RadiusWork rw = walk_radius(arena, nq, ns);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_radius_neighbors_async: scratch too small");
+  GridWork w = rw.w;
+  int *const counts = rw.counts, *const qstarts = rw.qstarts;
   const float cell = 1.01f * radius;   // as apr_radius_neighbors
   if (!reuse_grid) {
     int rc = build_grid(supports, ns, s_lengths_host, nb, cell, 1, w, st);

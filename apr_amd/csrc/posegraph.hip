@@ -20,7 +20,6 @@ constexpr int kInfoMaxProblems = 64;   // = the segment limit of the batched sea
 constexpr int kInfoBlock = 256;
 constexpr int kInfoSums = 10;          // n, x, y, z, xx, yy, zz, xy, xz, yz
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct InfoBatch {
   int nb;
@@ -168,16 +167,12 @@ struct InfoScratch {
 
 static int info_total_blocks(int64_t n_src_total, int nb) { return (int)(cdiv64(n_src_total, kInfoBlock) + nb); }
 
-static size_t info_carve(void* scratch, int64_t n, int64_t m, int nb, InfoScratch* out) {
-  char* p0 = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  char* p = p0;
-  out->grid = p;
-  p += align256(apr_internal_grid_bytes(m));
-  out->rows = (float4*)p;
-  p += align256((size_t)(m > 0 ? m : 1) * 16);
-  out->partial = (double*)p;
-  p += align256((size_t)info_total_blocks(n > 0 ? n : 1, nb) * kInfoSums * 8);
-  return (size_t)(p - p0) + 256;
+static InfoScratch info_walk(AprArena& a, int64_t n, int64_t m, int nb) {
+  InfoScratch s;
+  s.grid = a.take<char>(apr_internal_grid_bytes(m));      // points.hip's search grid: its own carve
+  s.rows = a.take<float4>(m > 0 ? m : 1);
+  s.partial = a.take<double>((size_t)info_total_blocks(n > 0 ? n : 1, nb) * kInfoSums);
+  return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -627,8 +622,9 @@ __global__ __launch_bounds__(kPgBlock) void k_posegraph(const int* __restrict__ 
 }  // namespace
 
 APR_API size_t apr_information_scratch_bytes(int64_t n_src_total, int64_t n_tgt_total, int32_t nb) {
-  InfoScratch s;
-  return info_carve(nullptr, n_src_total, n_tgt_total, nb > 0 ? nb : 1, &s);
+  AprArena a(nullptr);
+  info_walk(a, n_src_total, n_tgt_total, nb > 0 ? nb : 1);
+  return a.bytes();
 }
 
 APR_API int apr_information_batch(const float* src, const int64_t* src_offsets_host, const float* tgt,
@@ -651,7 +647,9 @@ APR_API int apr_information_batch(const float* src, const int64_t* src_offsets_h
   const int64_t n = src_offsets_host[nb], m = tgt_offsets_host[n_tgt];
   APR_CHECK_ARG(n < (1ll << 31) - kInfoBlock * (kInfoMaxProblems + 1) && m < (1ll << 31) - 1,
                 "apr_information_batch: oversized clouds");
-  APR_CHECK_ARG(scratch && scratch_bytes >= apr_information_scratch_bytes(n, m, nb), "apr_information_batch: scratch too small");
+  AprArena arena(scratch);
+  const InfoScratch w = info_walk(arena, n, m, nb);
+  APR_CHECK_ARG(scratch && arena.fits(scratch_bytes), "apr_information_batch: scratch too small");
   InfoBatch sg;
   sg.nb = nb;
   sg.blk0[0] = 0;
@@ -668,8 +666,6 @@ APR_API int apr_information_batch(const float* src, const int64_t* src_offsets_h
     sg.b0[i] = (int)tgt_offsets_host[i];
     if (i) tlen[i - 1] = (int32_t)(tgt_offsets_host[i] - tgt_offsets_host[i - 1]);
   }
-  InfoScratch w;
-  info_carve(scratch, n, m, nb, &w);
   const float rf = (float)max_dist;
   const float r2 = rf * rf;                      // the strict bound, in the precision of d^2
   AprSearchGrid g;

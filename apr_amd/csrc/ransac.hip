@@ -1188,65 +1188,42 @@ struct RansacScratch {
   int* live;                  // ... their counts and the NEAR / FAR list lengths (kLiveInts)
   int *order_near, *order_far;      // [cap] each
   unsigned char* near_flag;   // [cap]
-  char* end;
 };
 
 static int band_words(int64_t n0) { return (int)((rec2_rows(n0) / kMini + 31) / 32); }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// raw result = the best hypothesis with total_valid behind it: what apr_ransac_decode reads, and the head of every batch
+// result slot (stride kSlotBytes)
+constexpr size_t kRawBytes = sizeof(Hyp) + 8, kSlotBytes = sizeof(Hyp) + 64;
 
-static size_t ransac_core_bytes(int64_t n0, int64_t max_iter) {
-  const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
-  const size_t c1 = (size_t)(cap < 1 ? 1 : cap);
-  return 768 + align256(c1 * sizeof(Hyp)) + align256((size_t)n0 * 32) +
-         align256(((size_t)(max_iter < 1 ? 1 : max_iter) + kCandLists * 256) * 8) + align256(kGeoGrid * sizeof(GeoPart)) +
-         align256((size_t)rec2_rows(n0) * 48) + 256 + align256(c1 * 4) + align256(c1 * band_words(n0) * 4) +
-         align256(kSelParts * sizeof(SelPart)) + align256((size_t)(n0 + 32) * 8) + 256 + align256((size_t)n0 * 32) +
-         align256((size_t)rec2_rows(n0) * 48) + 256 + 2 * align256(c1 * 4) + align256(c1);
-}
-
-static RansacScratch carve_ransac(void* scratch, int64_t n0, int64_t max_iter) {
-  const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
+static RansacScratch walk_ransac(AprArena& a, int64_t n0, int64_t max_iter) {
+  if (max_iter < 1) max_iter = 1;
+  const size_t cap = (size_t)(max_iter < kChunk ? max_iter : kChunk);
   RansacScratch r;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  r.best = (Hyp*)p;
-  r.total_valid = (long long*)(p + sizeof(Hyp));
-  r.n_valid = (int*)(p + sizeof(Hyp) + 8);
-  r.n_cand = (int*)(p + 256);   // kCandLists counters; n_valid .. the last counter: ONE memset (kCountersBytes) clears them
-  r.live = (int*)(p + 512);     // ... and the pruned list's counters behind them (counter_words covers both)
-  p += 768;
-  r.hyps = (Hyp*)p;
-  p += align256((size_t)cap * sizeof(Hyp));
-  r.rec = (float4*)p;
-  p += align256((size_t)n0 * 32);
-  r.cand = (long long*)p;
-  p += align256(((size_t)max_iter + kCandLists * 256) * 8);
-  r.part = (GeoPart*)p;
-  p += align256(kGeoGrid * sizeof(GeoPart));
-  r.rec2 = (float*)p;
-  p += align256((size_t)rec2_rows(n0) * 48);
-  r.maxn2 = (unsigned*)p;
-  r.sel_hdr = (int*)p + 1;    // adjacent: one 12-byte memset clears the norm bound and the pick header
-  p += 256;
-  r.sel = (int*)p;
-  p += align256((size_t)cap * 4);
-  r.band = (unsigned*)p;
-  p += align256((size_t)cap * band_words(n0) * 4);
-  r.selp = (SelPart*)p;
-  p += align256(kSelParts * sizeof(SelPart));
-  r.rec8 = (unsigned long long*)p;
-  p += align256((size_t)(n0 + 32) * 8);
-  r.rec_live = (float4*)p;
-  p += align256((size_t)n0 * 32);
-  r.rec2_live = (float*)p;
-  p += align256((size_t)rec2_rows(n0) * 48);
-  r.order_near = (int*)p;
-  p += align256((size_t)cap * 4);
-  r.order_far = (int*)p;
-  p += align256((size_t)cap * 4);
-  r.near_flag = (unsigned char*)p;
-  p += align256((size_t)cap);
-  r.end = p;
+  // the 768-byte header is ONE block: best, total_valid, then n_valid .. the kCandLists candidate counters (at 256) .. the
+  // pruned list's `live` counters (at 512), contiguous for the one memset of counter_words
+  char* const h = a.take<char>(768);
+  r.best = (Hyp*)h;
+  r.total_valid = (long long*)(h + sizeof(Hyp));
+  r.n_valid = (int*)(h + kRawBytes);
+  r.n_cand = (int*)(h + 256);
+  r.live = (int*)(h + 512);
+  r.hyps = a.take<Hyp>(cap);
+  r.rec = a.take<float4>(2 * (size_t)n0);
+  r.cand = a.take<long long>((size_t)max_iter + kCandLists * 256);   // 256 entries of headroom per sub-list
+  r.part = a.take<GeoPart>(kGeoGrid);
+  r.rec2 = a.take<float>((size_t)rec2_rows(n0) * 12);                // rec2_rows(n0) rows of 12 floats
+  r.maxn2 = a.take<unsigned>(64);
+  r.sel_hdr = (int*)r.maxn2 + 1;    // adjacent: one 12-byte clear covers the norm bound and the pick header
+  r.sel = a.take<int>(cap);
+  r.band = a.take<unsigned>(cap * band_words(n0));
+  r.selp = a.take<SelPart>(kSelParts);
+  r.rec8 = a.take<unsigned long long>((size_t)n0 + 32);            // k_pack_small writes n0 + 32 rows
+  r.rec_live = a.take<float4>(2 * (size_t)n0);
+  r.rec2_live = a.take<float>((size_t)rec2_rows(n0) * 12);
+  r.order_near = a.take<int>(cap);
+  r.order_far = a.take<int>(cap);
+  r.near_flag = a.take<unsigned char>(cap);
   return r;
 }
 
@@ -1262,10 +1239,7 @@ static void launch_pack(const RansacScratch& r, const float* xyz0, const float* 
 // Which sampling kernel: k_sample_screen (default) takes the first edge out of a 112 KB table in LDS; it owns a CU's whole
 // LDS while it runs.  Whether that costs a pipelined caller more than it saves could not be settled on this repo's
 // benchmark (three same-box A/Bs: +0.8 %, -5 %, 0 %; with true matches in the set the screen is 6 % ahead), so the choice
-// is the caller's: apr_ransac_set_screen; -1 = APR_RANSAC_SCREEN from the environment (default 1, read once: the A/B
-// and test hook).
-static std::atomic<int> g_ransac_screen{-1};
-
+// is the caller's: option kOptScreen below (apr_ransac_set_screen / apr_ransac_set_option).
 // A/B and test switches: set through apr_ransac_set_option (an atomic each), defaults from the environment read ONCE per
 // process (round-4 advice: a getenv on every call from threads that run without the interpreter lock races with any
 // setenv / putenv of the host application, and Python's os.environ assignments are putenv calls)
@@ -1334,9 +1308,7 @@ static void launch_hypotheses(const RansacScratch& r, int64_t n0, double max_dis
   // many iterations over a table that fits the LDS: the first edge is screened there (k_sample_screen; same candidates).
   // APR_RANSAC_SCREEN=0 / apr_ransac_set_screen(0) keeps the plain kernel.
   const int64_t niter = it1 - it0;
-  const int screen_set = g_ransac_screen.load(std::memory_order_relaxed);
-  const int want_screen = screen_set >= 0 ? screen_set : ransac_opt(kOptScreen);
-  const bool screened = niter >= 64 * kScreenRound && n0 <= kScreenMaxN0 && want_screen && screen_ready();
+  const bool screened = niter >= 64 * kScreenRound && n0 <= kScreenMaxN0 && ransac_opt(kOptScreen) && screen_ready();
   g_sampling_launches[screened ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   if (screened) {
     const int64_t swg = 256;                                     // one 1024-thread workgroup per CU; a multiple of kCandLists
@@ -1352,28 +1324,60 @@ static void launch_hypotheses(const RansacScratch& r, int64_t n0, double max_dis
                      r.cand, r.n_cand, sub_cap, r.hyps, r.n_valid, cap);
 }
 
-static int fetch_result(const RansacScratch& r, double* result_host, long long* tv_out, hipStream_t st) {
+// the 20 doubles of a result from its raw form (kRawBytes); returns total_valid
+static long long decode_result(const void* raw, double* result_host) {
   Hyp hb;
-  long long tv = 0;
-  APR_HIP(hipMemcpyAsync(&hb, r.best, sizeof(Hyp), hipMemcpyDeviceToHost, st));
-  APR_HIP(hipMemcpyAsync(&tv, r.total_valid, 8, hipMemcpyDeviceToHost, st));
-  APR_HIP(hipStreamSynchronize(st));
+  long long tv;
+  memcpy(&hb, raw, sizeof(Hyp));
+  memcpy(&tv, (const char*)raw + sizeof(Hyp), 8);
   for (int k = 0; k < 12; ++k) result_host[k] = hb.T[k];
   result_host[12] = 0.0; result_host[13] = 0.0; result_host[14] = 0.0; result_host[15] = 1.0;
   result_host[16] = (double)(hb.inliers < 0 ? 0 : hb.inliers);
   result_host[17] = hb.inliers > 0 ? sqrt(hb.err2 / (double)hb.inliers) : 0.0;
   result_host[18] = (double)hb.it;
   result_host[19] = (double)tv;
-  *tv_out = tv;
+  return tv;
+}
+
+// the running best and total_valid to `raw` (kRawBytes; host or device memory), no synchronisation
+static int copy_raw(void* raw, const Hyp* best, const long long* total_valid, hipMemcpyKind kind, hipStream_t st) {
+  APR_HIP(hipMemcpyAsync(raw, best, sizeof(Hyp), kind, st));
+  APR_HIP(hipMemcpyAsync((char*)raw + sizeof(Hyp), total_valid, 8, kind, st));
   return APR_OK;
+}
+
+static int fetch_result(const Hyp* best, const long long* total_valid, double* result_host, hipStream_t st,
+                        long long* tv_out = nullptr) {
+  alignas(8) char raw[kRawBytes];
+  if (int rc = copy_raw(raw, best, total_valid, hipMemcpyDeviceToHost, st)) return rc;
+  APR_HIP(hipStreamSynchronize(st));
+  const long long tv = decode_result(raw, result_host);
+  if (tv_out) *tv_out = tv;
+  return APR_OK;
+}
+
+struct GeoScratch {
+  RansacScratch r;
+  int* selected;    // [cap]
+  void* grid;       // points.hip's search grid over xyz1: its own carve
+  GeoPart* part;    // [cap + kGeoGrid]
+};
+static GeoScratch walk_geometric(AprArena& a, int64_t n0, int64_t n1, int64_t max_iter) {
+  const size_t cap = (size_t)(max_iter < kChunk ? max_iter : kChunk);
+  GeoScratch g;
+  g.r = walk_ransac(a, n0, max_iter);
+  g.selected = a.take<int>(cap);
+  g.grid = a.take<char>(apr_internal_grid_bytes(n1));
+  g.part = a.take<GeoPart>(cap + kGeoGrid);
+  return g;
 }
 
 }  // namespace
 
 APR_API size_t apr_ransac_geometric_scratch_bytes(int64_t n0, int64_t n1, int64_t max_iter) {
-  const size_t cap = (size_t)(max_iter < kChunk ? max_iter : kChunk);
-  return ransac_core_bytes(n0, max_iter) + align256(cap * 4) + 256 + apr_internal_grid_bytes(n1) + 256 +
-         align256((cap + kGeoGrid) * sizeof(GeoPart));
+  AprArena a(nullptr);
+  walk_geometric(a, n0, n1, max_iter);
+  return a.bytes();
 }
 
 namespace {
@@ -1383,15 +1387,15 @@ int geometric_enqueue(const float* xyz0, int64_t n0, const float* xyz1, int64_t 
   APR_CHECK_ARG(n0 > 0 && n0 < (1ll << 31) && n1 > 0 && n1 < (1ll << 31), "apr_ransac_pose_geometric: empty point set");
   APR_CHECK_ARG(max_iter > 0 && max_iter <= kChunk && max_validation > 0 && max_dist > 0,
                 "apr_ransac_pose_geometric: need 0 < max_iter <= %lld and max_validation > 0", (long long)kChunk);
-  APR_CHECK_ARG(scratch_bytes >= apr_ransac_geometric_scratch_bytes(n0, n1, max_iter),
-                "apr_ransac_pose_geometric: scratch too small");
+  AprArena arena(scratch);
+  const GeoScratch gs = walk_geometric(arena, n0, n1, max_iter);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_ransac_pose_geometric: scratch too small");
   const int64_t cap = max_iter;
-  const RansacScratch r = carve_ransac(scratch, n0, max_iter);
-  int* selected = (int*)r.end;
-  void* grid_scratch = (void*)(r.end + align256((size_t)cap * 4));
-  GeoPart* part = (GeoPart*)((char*)grid_scratch + align256(apr_internal_grid_bytes(n1)) + 256);
+  const RansacScratch& r = gs.r;
+  int* const selected = gs.selected;
+  GeoPart* const part = gs.part;
   AprSearchGrid g;
-  int rc = apr_internal_search_grid(xyz1, n1, (float)(2.0 * max_dist), grid_scratch, &g, st);
+  int rc = apr_internal_search_grid(xyz1, n1, (float)(2.0 * max_dist), gs.grid, &g, st);
   if (rc != APR_OK) return rc;
   hipLaunchKernelGGL(k_init_best, dim3(1), dim3(1), 0, st, r.best, r.total_valid, r.maxn2, (int*)nullptr, 0);
   launch_pack(r, xyz0, xyz1, n1, corr, n0, st);
@@ -1408,14 +1412,6 @@ int geometric_enqueue(const float* xyz0, int64_t n0, const float* xyz1, int64_t 
   return APR_OK;
 }
 
-void decode_result(const Hyp& hb, long long tv, double* result_host) {
-  for (int k = 0; k < 12; ++k) result_host[k] = hb.T[k];
-  result_host[12] = 0.0; result_host[13] = 0.0; result_host[14] = 0.0; result_host[15] = 1.0;
-  result_host[16] = (double)(hb.inliers < 0 ? 0 : hb.inliers);
-  result_host[17] = hb.inliers > 0 ? sqrt(hb.err2 / (double)hb.inliers) : 0.0;
-  result_host[18] = (double)hb.it;
-  result_host[19] = (double)tv;
-}
 }  // namespace
 
 APR_API int apr_ransac_pose_geometric(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1,
@@ -1427,14 +1423,13 @@ APR_API int apr_ransac_pose_geometric(const float* xyz0, int64_t n0, const float
   int rc = geometric_enqueue(xyz0, n0, xyz1, n1, corr, max_dist, edge_ratio, max_iter, max_validation, seed, scratch,
                              scratch_bytes, &r, st);
   if (rc != APR_OK) return rc;
-  long long tv;
-  return fetch_result(r, result_host, &tv, st);
+  return fetch_result(r.best, r.total_valid, result_host, st);
 }
 
 // The same without the host synchronisation: the raw result (apr_ransac_raw_bytes() bytes) is copied to `raw_dev`, a
 // device buffer of the caller's, so that the scratch can serve the next pair at once; the caller fetches the raw
 // results of a whole batch with one copy and decodes them on the host with apr_ransac_decode.
-APR_API size_t apr_ransac_raw_bytes(void) { return sizeof(Hyp) + 8; }
+APR_API size_t apr_ransac_raw_bytes(void) { return kRawBytes; }
 
 APR_API int apr_ransac_pose_geometric_async(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1,
                                             const int64_t* corr, double max_dist, double edge_ratio, int64_t max_iter,
@@ -1446,22 +1441,20 @@ APR_API int apr_ransac_pose_geometric_async(const float* xyz0, int64_t n0, const
   int rc = geometric_enqueue(xyz0, n0, xyz1, n1, corr, max_dist, edge_ratio, max_iter, max_validation, seed, scratch,
                              scratch_bytes, &r, st);
   if (rc != APR_OK) return rc;
-  APR_HIP(hipMemcpyAsync(raw_dev, r.best, sizeof(Hyp), hipMemcpyDeviceToDevice, st));
-  APR_HIP(hipMemcpyAsync((char*)raw_dev + sizeof(Hyp), r.total_valid, 8, hipMemcpyDeviceToDevice, st));
-  return APR_OK;
+  return copy_raw(raw_dev, r.best, r.total_valid, hipMemcpyDeviceToDevice, st);
 }
 
 APR_API int apr_ransac_decode(const void* raw_host, double* result_host) {
   APR_CHECK_ARG(raw_host && result_host, "apr_ransac_decode: NULL argument");
-  Hyp hb;
-  long long tv;
-  memcpy(&hb, raw_host, sizeof(Hyp));
-  memcpy(&tv, (const char*)raw_host + sizeof(Hyp), 8);
-  decode_result(hb, tv, result_host);
+  decode_result(raw_host, result_host);
   return APR_OK;
 }
 
-APR_API size_t apr_ransac_scratch_bytes(int64_t n0, int64_t max_iter) { return ransac_core_bytes(n0, max_iter); }
+APR_API size_t apr_ransac_scratch_bytes(int64_t n0, int64_t max_iter) {
+  AprArena a(nullptr);
+  walk_ransac(a, n0, max_iter);
+  return a.bytes();
+}
 
 APR_API int apr_ransac_pose(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int64_t* corr,
                             double max_dist, double edge_ratio, int64_t max_iter, uint64_t seed, void* scratch,
@@ -1469,9 +1462,10 @@ APR_API int apr_ransac_pose(const float* xyz0, int64_t n0, const float* xyz1, in
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(n0 > 0 && n0 < (1ll << 31) && n1 > 0, "apr_ransac_pose: empty point set");
   APR_CHECK_ARG(max_iter > 0 && max_iter < (1ll << 31) && max_dist > 0, "apr_ransac_pose: bad max_iter / max_dist");
-  APR_CHECK_ARG(scratch_bytes >= apr_ransac_scratch_bytes(n0, max_iter), "apr_ransac_pose: scratch too small");
+  AprArena arena(scratch);
+  const RansacScratch r = walk_ransac(arena, n0, max_iter);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_ransac_pose: scratch too small");
   const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
-  const RansacScratch r = carve_ransac(scratch, n0, max_iter);
   const double thr_lt = sqrt_lt_threshold(max_dist);
   hipLaunchKernelGGL(k_init_best, dim3(1), dim3(1), 0, st, r.best, r.total_valid, r.maxn2, (int*)nullptr, 0);   // clears the norm bound + pick header
   launch_pack(r, xyz0, xyz1, n1, corr, n0, st);
@@ -1492,7 +1486,7 @@ APR_API int apr_ransac_pose(const float* xyz0, int64_t n0, const float* xyz1, in
     }
     APR_LAUNCH_CHECK();
     long long tv;
-    int rc = fetch_result(r, result_host, &tv, st);
+    int rc = fetch_result(r.best, r.total_valid, result_host, st, &tv);
     if (rc != APR_OK) return rc;
     if (tv <= cap || step == cap) break;   // nothing was dropped
   }
@@ -1530,43 +1524,39 @@ int match_lanes(int32_t B) {
   return B < l ? B : l;
 }
 
-struct BatchLayout {
-  size_t nn_scratch, best, ransac, lane, slots, corr_each, total;   // lane = nn_scratch + best + ransac, once per lane
-  int lanes;
-};
-
-BatchLayout batch_layout(int32_t B, int64_t n0_max, int64_t n1_max, int32_t c, int64_t max_iter) {
-  BatchLayout L;
-  L.lanes = match_lanes(B);
-  L.nn_scratch = align256(apr_feature_nn_fast_scratch_bytes(n0_max, n1_max, c) + 256);
-  L.best = align256((size_t)n0_max * 8);
-  L.ransac = align256(ransac_core_bytes(n0_max, max_iter) + 256);
-  L.lane = L.nn_scratch + L.best + L.ransac;
-  L.slots = align256((size_t)B * (sizeof(Hyp) + 64));
-  L.corr_each = align256((size_t)n0_max * 8);
-  L.total = (size_t)L.lanes * L.lane + L.slots + (size_t)B * L.corr_each + 512;
-  return L;
-}
-
 // Scratch layout: [result slots][correspondences of the B pairs][lane 0][lane 1] ...  Everything apr_match_pose_batch_finish
 // reads (slots, correspondences, lane 0's RANSAC scratch for the overflow replay) sits at positions that do NOT depend on
 // the lane count, and the enqueue call uses as many lanes as the scratch it was handed holds -- so a change of
 // apr_match_pose_set_lanes between scratch_bytes / enqueue / finish of a batch in flight can cost lanes, never correctness.
-struct BatchViews {
-  char *slots, *corr_base, *lane_base;
+struct BatchScratch {
+  char *slots, *corr, *lane0;      // [B] kSlotBytes each, [B] corr_each each, [lanes] lane_bytes each
+  size_t corr_each, nn_bytes, best_off, ransac_off, ransac_bytes, lane_bytes;   // a lane: [feature NN][packed best][RANSAC]
   int lanes;
 };
 
-BatchViews batch_views(const BatchLayout& L, int32_t B, void* scratch, size_t scratch_bytes) {
-  BatchViews v;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  v.slots = p;                          p += L.slots;
-  v.corr_base = p;                      p += (size_t)B * L.corr_each;
-  v.lane_base = p;
-  const size_t used = (size_t)(p - (char*)scratch);
-  const size_t fit = scratch_bytes > used ? (scratch_bytes - used) / L.lane : 0;
-  v.lanes = (int)(fit < (size_t)L.lanes ? fit : (size_t)L.lanes);
-  return v;
+// The sizing walk takes match_lanes(B) lanes; a carve takes as many of them as `scratch_bytes` holds (0: scratch too small).
+BatchScratch walk_batch(AprArena& a, size_t scratch_bytes, int32_t B, int64_t n0_max, int64_t n1_max, int32_t c,
+                        int64_t max_iter) {
+  BatchScratch s;
+  s.slots = a.take<char>((size_t)B * kSlotBytes);
+  s.corr_each = apr_align256((size_t)n0_max * 8);
+  s.corr = a.take<char>((size_t)B * s.corr_each);
+  AprArena lane(nullptr);      // each piece is a carve of its own behind an aligned base
+  s.nn_bytes = apr_feature_nn_fast_scratch_bytes(n0_max, n1_max, c);
+  lane.take<char>(s.nn_bytes);
+  s.best_off = lane.off;
+  lane.take<uint64_t>((size_t)n0_max);
+  s.ransac_off = lane.off;
+  s.ransac_bytes = apr_ransac_scratch_bytes(n0_max, max_iter);
+  lane.take<char>(s.ransac_bytes);
+  s.lane_bytes = lane.off;
+  s.lanes = match_lanes(B);
+  if (a.base) {
+    const size_t fit = scratch_bytes > a.bytes() ? (scratch_bytes - a.bytes()) / s.lane_bytes : 0;
+    if (fit < (size_t)s.lanes) s.lanes = (int)fit;
+  }
+  s.lane0 = a.take<char>((size_t)s.lanes * s.lane_bytes);
+  return s;
 }
 
 // Library-owned side streams, kMaxLanes - 1 per (device, caller stream), created on first use and kept for the life of
@@ -1598,8 +1588,7 @@ int side_streams(hipStream_t caller, SideStreams* out) {
 // environment's APR_RANSAC_SCREEN (default 1).  Same candidates either way.  Takes effect for the calls that follow.
 APR_API int apr_ransac_set_screen(int32_t mode) {
   APR_CHECK_ARG(mode >= -1 && mode <= 1, "apr_ransac_set_screen: mode -1, 0 or 1");
-  g_ransac_screen.store(mode, std::memory_order_relaxed);
-  return APR_OK;
+  return apr_ransac_set_option(kOptScreen, mode);
 }
 
 // The sampling kernel that actually RAN: launch counts since load, out[0] = k_sample_check, out[1] = k_sample_screen (the
@@ -1610,7 +1599,6 @@ APR_API int apr_ransac_set_screen(int32_t mode) {
 // (APR_RANSAC_SCREEN / _COUNT / _PRUNE / _FORCE_ROUNDS, read once per process).  Same results whatever the settings.
 APR_API int apr_ransac_set_option(int32_t option, int32_t value) {
   APR_CHECK_ARG(option >= 0 && option < kOptN && value >= -1 && value <= 1, "apr_ransac_set_option: option 0 .. 3, value -1, 0 or 1");
-  if (option == kOptScreen) g_ransac_screen.store(value, std::memory_order_relaxed);
   g_ransac_opt[option].store(value, std::memory_order_relaxed);
   return APR_OK;
 }
@@ -1631,10 +1619,12 @@ APR_API int apr_match_pose_set_lanes(int32_t lanes) {
 APR_API size_t apr_match_pose_batch_scratch_bytes(int32_t B, int64_t n0_max, int64_t n1_max, int32_t c,
                                                   int64_t max_iter) {
   if (B <= 0 || n0_max <= 0 || n1_max <= 0 || c <= 0 || max_iter <= 0) return 0;
-  return batch_layout(B, n0_max, n1_max, c, max_iter).total;
+  AprArena a(nullptr);
+  walk_batch(a, 0, B, n0_max, n1_max, c, max_iter);
+  return a.bytes();
 }
 
-APR_API size_t apr_match_pose_batch_slot_bytes(int32_t B) { return B > 0 ? (size_t)B * (sizeof(Hyp) + 64) : 0; }
+APR_API size_t apr_match_pose_batch_slot_bytes(int32_t B) { return B > 0 ? (size_t)B * kSlotBytes : 0; }
 
 // Everything of apr_match_pose_batch up to the copy of the B result slots into slots_host (pinned memory of
 // apr_match_pose_batch_slot_bytes(B) bytes for the copy to be asynchronous): NO host synchronisation.
@@ -1651,13 +1641,11 @@ APR_API int apr_match_pose_batch_enqueue(const apr_pair_desc* pairs, int32_t B, 
     n0_max = pairs[i].n0 > n0_max ? pairs[i].n0 : n0_max;
     n1_max = pairs[i].n1 > n1_max ? pairs[i].n1 : n1_max;
   }
-  const BatchLayout L = batch_layout(B, n0_max, n1_max, c, max_iter);
-  const BatchViews V = batch_views(L, B, scratch, scratch_bytes);
-  APR_CHECK_ARG(V.lanes >= 1, "apr_match_pose_batch: scratch too small");
-  const int nlanes = V.lanes;
-  char* const lane_base = V.lane_base;
-  char* const slots = V.slots;
-  char* const corr_base = V.corr_base;
+  AprArena arena(scratch);
+  const BatchScratch L = walk_batch(arena, scratch_bytes, B, n0_max, n1_max, c, max_iter);
+  APR_CHECK_ARG(L.lanes >= 1, "apr_match_pose_batch: scratch too small");
+  const int nlanes = L.lanes;
+  char* const slots = L.slots;
   const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
   const double thr_lt = sqrt_lt_threshold(max_dist);
   const bool fast_nn = (c == 32 || c == 64 || c == 128);
@@ -1683,17 +1671,16 @@ APR_API int apr_match_pose_batch_enqueue(const apr_pair_desc* pairs, int32_t B, 
     const apr_pair_desc& d = pairs[i];
     const int l = i % nlanes;
     hipStream_t ls = lane_st[l];
-    char* lp = lane_base + (size_t)l * L.lane;
-    void* nn_scratch = lp;
-    uint64_t* best = (uint64_t*)(lp + L.nn_scratch);
-    void* ransac_scratch = lp + L.nn_scratch + L.best;
-    rc = fast_nn ? apr_feature_nn_fast(d.f0, d.n0, d.f1, d.n1, c, best, nn_scratch, L.nn_scratch, ls)
+    char* lp = L.lane0 + (size_t)l * L.lane_bytes;
+    uint64_t* best = (uint64_t*)(lp + L.best_off);
+    rc = fast_nn ? apr_feature_nn_fast(d.f0, d.n0, d.f1, d.n1, c, best, lp, L.nn_bytes, ls)
                  : apr_feature_nn(d.f0, d.n0, d.f1, d.n1, c, best, ls);
     if (rc != APR_OK) break;
-    int64_t* corr = (int64_t*)(corr_base + (size_t)i * L.corr_each);     // plain indices: written by k_pack_pairs below
+    int64_t* corr = (int64_t*)(L.corr + (size_t)i * L.corr_each);     // plain indices: written by k_pack_pairs below
     // single-round RANSAC into this pair's result slot
-    RansacScratch r = carve_ransac(ransac_scratch, d.n0, max_iter);
-    r.best = (Hyp*)(slots + (size_t)i * (sizeof(Hyp) + 64));
+    AprArena ra(lp + L.ransac_off);
+    RansacScratch r = walk_ransac(ra, d.n0, max_iter);
+    r.best = (Hyp*)(slots + (size_t)i * kSlotBytes);
     r.total_valid = (long long*)((char*)r.best + sizeof(Hyp));
     hipLaunchKernelGGL(k_init_best, dim3(1), dim3(128), 0, ls, r.best, r.total_valid, r.maxn2, r.n_valid, counter_words(r));
     launch_pack(r, d.xyz0, d.xyz1, d.n1, (const int64_t*)best, d.n0, ls, corr);
@@ -1711,7 +1698,7 @@ APR_API int apr_match_pose_batch_enqueue(const apr_pair_desc* pairs, int32_t B, 
   }
   if (rc != APR_OK) return rc;
   APR_LAUNCH_CHECK();
-  APR_HIP(hipMemcpyAsync(slots_host, slots, (size_t)B * (sizeof(Hyp) + 64), hipMemcpyDeviceToHost, st));
+  APR_HIP(hipMemcpyAsync(slots_host, slots, (size_t)B * kSlotBytes, hipMemcpyDeviceToHost, st));
   return APR_OK;
 }
 
@@ -1727,33 +1714,19 @@ APR_API int apr_match_pose_batch_finish(const apr_pair_desc* pairs, int32_t B, i
     n0_max = pairs[i].n0 > n0_max ? pairs[i].n0 : n0_max;
     n1_max = pairs[i].n1 > n1_max ? pairs[i].n1 : n1_max;
   }
-  const BatchLayout L = batch_layout(B, n0_max, n1_max, c, max_iter);
-  const BatchViews V = batch_views(L, B, scratch, scratch_bytes);
-  APR_CHECK_ARG(V.lanes >= 1, "apr_match_pose_batch: scratch too small");
-  void* ransac_scratch = V.lane_base + L.nn_scratch + L.best;      // lane 0's
-  char* const corr_base = V.corr_base;
+  AprArena arena(scratch);
+  const BatchScratch L = walk_batch(arena, scratch_bytes, B, n0_max, n1_max, c, max_iter);
+  APR_CHECK_ARG(L.lanes >= 1, "apr_match_pose_batch: scratch too small");
   const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
-  const size_t slot_bytes = sizeof(Hyp) + 64;
-  const char* host = (const char*)slots_host;
   int rc = APR_OK;
   for (int i = 0; i < B && rc == APR_OK; ++i) {
-    Hyp hb;
-    long long tv;
-    memcpy(&hb, host + (size_t)i * slot_bytes, sizeof(Hyp));
-    memcpy(&tv, host + (size_t)i * slot_bytes + sizeof(Hyp), 8);
     double* out = results_host + (size_t)i * 20;
+    const long long tv = decode_result((const char*)slots_host + (size_t)i * kSlotBytes, out);
     if (tv > cap && max_iter > cap) {   // hypothesis list overflowed: chunked rounds through the regular entry point
       const apr_pair_desc& d = pairs[i];
-      rc = apr_ransac_pose(d.xyz0, d.n0, d.xyz1, d.n1, (const int64_t*)(corr_base + (size_t)i * L.corr_each), max_dist,
-                           edge_ratio, max_iter, d.seed, ransac_scratch, L.ransac, out, stream);
-      continue;
+      rc = apr_ransac_pose(d.xyz0, d.n0, d.xyz1, d.n1, (const int64_t*)(L.corr + (size_t)i * L.corr_each), max_dist,
+                           edge_ratio, max_iter, d.seed, L.lane0 + L.ransac_off, L.ransac_bytes, out, stream);      // lane 0's
     }
-    for (int k = 0; k < 12; ++k) out[k] = hb.T[k];
-    out[12] = 0.0; out[13] = 0.0; out[14] = 0.0; out[15] = 1.0;
-    out[16] = (double)(hb.inliers < 0 ? 0 : hb.inliers);
-    out[17] = hb.inliers > 0 ? sqrt(hb.err2 / (double)hb.inliers) : 0.0;
-    out[18] = (double)hb.it;
-    out[19] = (double)tv;
   }
   return rc;
 }
@@ -1872,22 +1845,17 @@ struct PairsScratch {
 
 int64_t pairs_iterations(int64_t max_iter, int64_t max_validation) { return max_iter < max_validation ? max_iter : max_validation; }
 
-PairsScratch carve_pairs(void* scratch, int64_t n1, int64_t np, int64_t n_iter) {
+PairsScratch walk_pairs(AprArena& a, int64_t n1, int64_t np, int64_t n_iter) {
   PairsScratch r;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  r.best = (Hyp*)p;
-  r.total_valid = (long long*)(p + sizeof(Hyp));
-  r.n_valid = (int*)(p + sizeof(Hyp) + 8);
-  p += 256;
-  r.hyps = (Hyp*)p;
-  p += align256((size_t)n_iter * sizeof(Hyp));
-  r.rec = (float4*)p;
-  p += align256((size_t)np * 32);
-  r.selected = (int*)p;
-  p += align256((size_t)n_iter * 4);
-  r.part = (GeoPart*)p;
-  p += align256((size_t)(n_iter + kGeoGrid) * sizeof(GeoPart));
-  r.grid = (void*)p;
+  char* const h = a.take<char>(kRawBytes + 4);      // the header is one block: best, total_valid, n_valid
+  r.best = (Hyp*)h;
+  r.total_valid = (long long*)(h + sizeof(Hyp));
+  r.n_valid = (int*)(h + kRawBytes);
+  r.hyps = a.take<Hyp>(n_iter);
+  r.rec = a.take<float4>(2 * (size_t)np);
+  r.selected = a.take<int>(n_iter);
+  r.part = a.take<GeoPart>(n_iter + kGeoGrid);
+  r.grid = a.take<char>(apr_internal_grid_bytes(n1));      // points.hip's search grid: its own carve
   return r;
 }
 
@@ -1897,9 +1865,9 @@ APR_API size_t apr_ransac_pairs_geometric_scratch_bytes(int64_t n0, int64_t n1, 
                                                         int64_t max_validation) {
   const int64_t n_iter = pairs_iterations(max_iter, max_validation);
   if (n0 <= 0 || n1 <= 0 || n_pairs < 0 || n_iter <= 0 || n_iter > kPairsMaxIter) return 0;
-  const size_t np = (size_t)(n_pairs < 1 ? 1 : n_pairs);
-  return 256 + 256 + align256((size_t)n_iter * sizeof(Hyp)) + align256(np * 32) + align256((size_t)n_iter * 4) +
-         align256((size_t)(n_iter + kGeoGrid) * sizeof(GeoPart)) + apr_internal_grid_bytes(n1) + 256;
+  AprArena a(nullptr);
+  walk_pairs(a, n1, n_pairs < 1 ? 1 : n_pairs, n_iter);
+  return a.bytes();
 }
 
 APR_API int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int32_t* pairs,
@@ -1915,15 +1883,15 @@ APR_API int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const
                 (long long)kPairsMaxIter);
   APR_CHECK_ARG(xyz0 && xyz1 && result_host && (pairs || n_pairs == 0), "apr_ransac_pose_pairs_geometric: NULL argument");
   if (n_pairs < 4) {      // open3d: corres.size() < ransac_n -> RegistrationResult()
-    Hyp hb;
-    for (int k = 0; k < 12; ++k) hb.T[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    hb.it = -1; hb.inliers = 0; hb.pad = 0; hb.err2 = 0.0;
-    decode_result(hb, 0, result_host);
+    struct { Hyp hb; long long tv; } raw = {};
+    for (int k = 0; k < 12; ++k) raw.hb.T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    raw.hb.it = -1;
+    decode_result(&raw, result_host);
     return APR_OK;
   }
-  APR_CHECK_ARG(scratch && scratch_bytes >= apr_ransac_pairs_geometric_scratch_bytes(n0, n1, n_pairs, max_iter, max_validation),
-                "apr_ransac_pose_pairs_geometric: scratch too small");
-  const PairsScratch r = carve_pairs(scratch, n1, n_pairs, n_iter);
+  AprArena arena(scratch);
+  const PairsScratch r = walk_pairs(arena, n1, n_pairs, n_iter);
+  APR_CHECK_ARG(scratch && arena.fits(scratch_bytes), "apr_ransac_pose_pairs_geometric: scratch too small");
   AprSearchGrid g;
   int rc = apr_internal_search_grid(xyz1, n1, (float)(2.0 * max_dist), r.grid, &g, st);
   if (rc != APR_OK) return rc;
@@ -1938,11 +1906,5 @@ APR_API int apr_ransac_pose_pairs_geometric(const float* xyz0, int64_t n0, const
                      (int)n_iter, n0, r.selected, r.part);
   hipLaunchKernelGGL(k_select, dim3(1), dim3(1024), 0, st, r.hyps, r.n_valid, (int)n_iter, r.best, r.total_valid);
   APR_LAUNCH_CHECK();
-  Hyp hb;
-  long long tv = 0;
-  APR_HIP(hipMemcpyAsync(&hb, r.best, sizeof(Hyp), hipMemcpyDeviceToHost, st));
-  APR_HIP(hipMemcpyAsync(&tv, r.total_valid, 8, hipMemcpyDeviceToHost, st));
-  APR_HIP(hipStreamSynchronize(st));
-  decode_result(hb, tv, result_host);
-  return APR_OK;
+  return fetch_result(r.best, r.total_valid, result_host, st);
 }

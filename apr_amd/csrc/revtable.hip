@@ -92,8 +92,6 @@ __global__ void k_rev_gather_range(const float* __restrict__ src, int c, const i
   *reinterpret_cast<f32x4*>(out + s * ldo + col) = acc;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t sort_temp_bytes(int64_t total, int bits) {
   size_t tmp = 0;
   (void)rocprim::radix_sort_pairs((void*)nullptr, tmp, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr,
@@ -107,12 +105,28 @@ int key_bits(int64_t ns) {
   return b;
 }
 
+struct RevScratch {
+  int *keys, *keys_sorted, *vals;   // [total] each
+  void* tmp;                        // rocprim's temporary storage
+  size_t tmp_bytes;
+};
+RevScratch walk_rev(AprArena& a, int64_t total, int bits) {
+  RevScratch r;
+  r.keys = a.take<int>(total);
+  r.keys_sorted = a.take<int>(total);
+  r.vals = a.take<int>(total);
+  r.tmp_bytes = sort_temp_bytes(total, bits);
+  r.tmp = a.take<char>(r.tmp_bytes);
+  return r;
+}
+
 }  // namespace
 
 APR_API size_t apr_reverse_table_scratch_bytes(int64_t nq, int32_t H, int64_t ns) {
   if (nq <= 0 || H <= 0 || ns <= 0) return 0;
-  const int64_t total = nq * H;
-  return 3 * al256((size_t)total * 4) + al256(sort_temp_bytes(total, key_bits(ns))) + 512;
+  AprArena a(nullptr);
+  walk_rev(a, nq * H, key_bits(ns));
+  return a.bytes();
 }
 
 // nbr i32 [nq, H] (entries outside [0, ns) = padding) -> rev_t i32 [nq * H] (flat positions sorted by the row they point at,
@@ -122,19 +136,15 @@ APR_API int apr_reverse_table_build(const int32_t* nbr, int64_t nq, int32_t H, i
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(nbr && rev_t && start && scratch && nq > 0 && H > 0 && ns > 0 && nq * (int64_t)H < (1ll << 31) && ns < (1ll << 30),
                 "apr_reverse_table_build: bad arguments");
-  APR_CHECK_ARG(scratch_bytes >= apr_reverse_table_scratch_bytes(nq, H, ns), "apr_reverse_table_build: scratch too small");
   const int64_t total = nq * H;
-  char* p = (char*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-  int* keys = (int*)p;          p += al256((size_t)total * 4);
-  int* keys_sorted = (int*)p;   p += al256((size_t)total * 4);
-  int* vals = (int*)p;          p += al256((size_t)total * 4);
-  void* tmp = p;
   const int bits = key_bits(ns);
-  size_t tmp_bytes = sort_temp_bytes(total, bits);
-  hipLaunchKernelGGL(k_rev_keys, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, nbr, total, (int)ns, keys, vals);
-  APR_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, (const int*)keys, keys_sorted, (const int*)vals, rev_t, (size_t)total, 0u,
+  AprArena arena(scratch);
+  RevScratch r = walk_rev(arena, total, bits);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_reverse_table_build: scratch too small");
+  hipLaunchKernelGGL(k_rev_keys, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, nbr, total, (int)ns, r.keys, r.vals);
+  APR_HIP(rocprim::radix_sort_pairs(r.tmp, r.tmp_bytes, (const int*)r.keys, r.keys_sorted, (const int*)r.vals, rev_t, (size_t)total, 0u,
                                     (unsigned)bits, st));
-  hipLaunchKernelGGL(k_rev_starts, dim3((unsigned)cdiv64(ns + 1, 256)), dim3(256), 0, st, keys_sorted, total, (int)ns, start);
+  hipLaunchKernelGGL(k_rev_starts, dim3((unsigned)cdiv64(ns + 1, 256)), dim3(256), 0, st, r.keys_sorted, total, (int)ns, start);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }

@@ -43,13 +43,11 @@ struct OsViews {
   unsigned* pair;    // [ntiles][K][R]
 };
 
-__host__ __device__ inline size_t os_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __host__ __device__ inline OsViews os_carve(void* blob, int64_t ntiles) {
   OsViews v;
   v.cnt = (int*)blob;
-  v.sched = (unsigned*)((char*)blob + os_align256((size_t)ntiles * 32 * 4));
-  v.pair = (unsigned*)((char*)v.sched + os_align256((size_t)ntiles * kSched * 4));
+  v.sched = (unsigned*)((char*)blob + apr_align256((size_t)ntiles * 32 * 4));
+  v.pair = (unsigned*)((char*)v.sched + apr_align256((size_t)ntiles * kSched * 4));
   return v;
 }
 
@@ -398,7 +396,7 @@ APR_API int32_t apr_spconv_os_tile_rows(int64_t n_out, int32_t cin, int32_t cout
 APR_API size_t apr_spconv_os_pairs_bytes(int64_t n_out, int32_t K, int32_t R) {
   if (n_out <= 0 || R <= 0 || K <= 0) return 0;
   const int64_t ntiles = cdiv64(n_out, R);
-  return os_align256((size_t)ntiles * 32 * 4) + os_align256((size_t)ntiles * kSched * 4) + (size_t)ntiles * K * R * 4 + 256;
+  return apr_align256((size_t)ntiles * 32 * 4) + apr_align256((size_t)ntiles * kSched * 4) + (size_t)ntiles * K * R * 4 + 256;
 }
 
 // nbr [n_out, K] (input rows < n_in < 2^23) -> per-tile pair lists in `blob` (apr_spconv_os_pairs_bytes)

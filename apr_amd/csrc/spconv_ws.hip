@@ -37,8 +37,6 @@ struct PairHeader {
   int cnt[32 * kCntStride];
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PairViews {
   PairHeader* hdr;
   int* pair_in;   // [K, n_out] input row of each pair
@@ -51,7 +49,7 @@ __host__ __device__ inline PairViews carve_pairs(int32_t* counters, void* blob, 
   v.hdr = (PairHeader*)counters;
   const size_t cap = (size_t)n_out * K;
   v.pair_in = (int*)p;
-  p += align256(cap * 4);
+  p += apr_align256(cap * 4);
   v.pair_id = (int*)p;
   return v;
 }
@@ -506,7 +504,7 @@ __host__ __device__ inline Pair3Views carve_pairs3(int32_t* counters, void* blob
   Pair3Views v;
   v.hdr = (PairHeader*)counters;
   v.ent = (int*)blob;
-  v.pair_id = (int*)((char*)blob + align256((size_t)n_out * 9 * 12));
+  v.pair_id = (int*)((char*)blob + apr_align256((size_t)n_out * 9 * 12));
   return v;
 }
 
@@ -817,7 +815,7 @@ APR_API int apr_spconv_pack_weights_bf3(const float* w, int32_t K, int32_t cin, 
 APR_API int32_t apr_pairlist_counter_ints(void) { return 32 * kCntStride; }
 
 APR_API size_t apr_pairlist_bytes(int64_t n_out, int32_t K) {
-  return 2 * align256((size_t)(n_out > 0 ? n_out : 1) * K * 4) + 256;
+  return 2 * apr_align256((size_t)(n_out > 0 ? n_out : 1) * K * 4) + 256;
 }
 
 APR_API int apr_pairlist_build(const int32_t* nbr, int64_t n_out, int32_t K, int32_t* counters, void* plist,
@@ -927,7 +925,7 @@ static int ws_fwd(const float* in, int64_t ldi, const int32_t* counters, const v
 // ---- triple pair lists (3^3 maps): half the product rows; see k_ws3_gemm_bf3 ----
 APR_API size_t apr_pairlist3_bytes(int64_t n_out) {
   const size_t n = (size_t)(n_out > 0 ? n_out : 1);
-  return align256(n * 9 * 12) + align256(n * 9 * 4) + 256;
+  return apr_align256(n * 9 * 12) + apr_align256(n * 9 * 4) + 256;
 }
 
 APR_API int apr_pairlist3_build(const int32_t* nbr, int64_t n_out, int32_t K, int32_t* counters, void* plist3,

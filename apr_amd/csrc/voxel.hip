@@ -32,7 +32,6 @@ constexpr int kVoxBigLds = 8192;               // rows the big kernel sorts in L
 constexpr int kVoxBigStage = 1024;             // rows it stages per round
 constexpr double kVoxMaxIndex = 131071.0;      // APR_AXIS_RANGE - APR_AXIS_BIAS - 1: indices are >= 0 by construction
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The statements that carry the contract switch contraction off for their body (DESIGN sections 16, 18: the __d*_rn
 // intrinsics are plain operators in this toolchain and fuse like any other expression).
@@ -322,9 +321,23 @@ __global__ __launch_bounds__(kMeanThreads) void k_cloud_mean(const float* __rest
 
 }  // namespace
 
+namespace {
+struct VoxelScratch {
+  void* grid;           // points.hip's bucket build: its own carve
+  long long* first64;   // [n] first row of every cell
+};
+VoxelScratch walk_voxel(AprArena& a, int64_t n) {
+  VoxelScratch v;
+  v.grid = a.take<char>(apr_internal_grid_bytes(n));
+  v.first64 = a.take<long long>(n);
+  return v;
+}
+}  // namespace
+
 APR_API size_t apr_voxel_down_sample_scratch_bytes(int64_t n) {
-  if (n < 1) n = 1;
-  return apr_internal_grid_bytes(n) + align256((size_t)n * 8) + 256;
+  AprArena a(nullptr);
+  walk_voxel(a, n < 1 ? 1 : n);
+  return a.bytes();
 }
 
 APR_API int apr_voxel_down_sample(const float* pts, int64_t n, const int32_t* lengths_host, int32_t nb, double voxel_size,
@@ -334,15 +347,17 @@ APR_API int apr_voxel_down_sample(const float* pts, int64_t n, const int32_t* le
   APR_CHECK_ARG(pts && lengths_host && scratch && n > 0 && n < (1ll << 31) && nb > 0 && nb <= kMaxBatch &&
                     voxel_size > 0.0 && voxel_size < __builtin_inf(),
                 "apr_voxel_down_sample: bad arguments");
-  APR_CHECK_ARG(scratch_bytes >= apr_voxel_down_sample_scratch_bytes(n), "apr_voxel_down_sample: scratch too small");
+  AprArena arena(scratch);
+  const VoxelScratch v = walk_voxel(arena, n);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_voxel_down_sample: scratch too small");
   for (int b = 0; b < nb; ++b) APR_CHECK_ARG(lengths_host[b] > 0, "apr_voxel_down_sample: empty cloud in batch");
   AprCellBuckets g;
-  int rc = apr_internal_buckets_begin(pts, n, lengths_host, nb, scratch, &g, st);
+  int rc = apr_internal_buckets_begin(pts, n, lengths_host, nb, v.grid, &g, st);
   if (rc != APR_OK) return rc;
-  long long* first64 = (long long*)((char*)scratch + apr_internal_grid_bytes(n));
+  long long* const first64 = v.first64;
   const unsigned nblk = (unsigned)cdiv64(n, kBlock);
   hipLaunchKernelGGL(k_vox_coords, dim3(nblk), dim3(kBlock), 0, st, pts, n, g.starts, nb, g.mins, voxel_size, g.coords);
-  rc = apr_internal_buckets_finish(n, scratch, (int64_t*)first64, st);
+  rc = apr_internal_buckets_finish(n, v.grid, (int64_t*)first64, st);
   if (rc != APR_OK) return rc;
   if (centroid || centroid32) {
     const unsigned grid = (unsigned)(cdiv64(n, 4) < 4096 ? cdiv64(n, 4) : 4096);
