@@ -183,6 +183,12 @@ PROTOTYPES = {
     "apr_valid_pair": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _f32, _p, _i64, _i64, _p, _sz, _p]),
     "apr_valid_pair_scratch_bytes": (_sz, [_i64]),
     "apr_contrastive_reduce": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _f32, _f32, _p, _p]),
+    "apr_pair_rows_from_nn": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
+    "apr_pair_dist": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p]),
+    "apr_pair_terms_scratch_bytes": (_sz, [_i64]),
+    "apr_pair_terms_reduce": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _f32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "apr_pair_grad_scratch_bytes": (_sz, [_i64, _i64, _i64]),
+    "apr_pair_grad": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "apr_grid_subsample_scratch_bytes": (_sz, [_i64]),
     "apr_grid_subsample": (C.c_int, [_p, _i64, _p, _i32, _f32, _p, _i32, _p, _p, _p, _p, _sz, _p]),
     "apr_grid_subsample_async": (C.c_int, [_p, _i64, _p, _i32, _f32, _p, _i32, _p, _p, _p, _p, _sz, _p]),

@@ -3,7 +3,10 @@ KITTINMComplementPairDataset.__getitem__ out, and its collate (FCGF_APR/lib/comp
 
   sample_random_trans        <- :29-38
   training_sample            <- :576-579, 596-716
+  pair_sample                <- :751-822 (the plain branch: no complement frames)
   collate_complement_pair_fn <- :1224-1279
+  collate_debug_pair_fn      <- :1282-1333
+  collate_pair_fn            <- FCGF_APR/lib/data_loaders.py:26-78
 
 Host orchestration of kernels that exist: apr_transform_points, apr_crop_to_radius, the voxel hash (sparse_quantize's
 first rows), the radius search behind get_matching_indices, and apr_cloud_mean for the one reduction the reference does in
@@ -130,3 +133,78 @@ def collate_complement_pair_fn(list_data):
         'T_gt': torch.cat(trans_batch, 0).float(),
         'len_batch': len_batch,
     }
+
+
+def pair_sample(xyz_0, xyz_1, M2, config, randg, pyrng=random, random_rotation=True, random_scale=True):
+    """:751-822 for one pair, the branch the FCGF baseline trainers' loader takes (no complement frames).  Host draws in
+    the reference's order: sample_random_trans for frame 0 then frame 1 (randg; :754-755, `rotation_range` pi / 4 read as
+    degrees), then pyrng.random() < 0.95 and, if so, pyrng.random() for the scale (:775-777).  Composed from what
+    training_sample uses; `downsample_single` and the `transform` hook stay with the caller.
+    -> (xyz_0 f32 [n0,3], xyz_1, coords_0 int32 [n0,3], coords_1, feats_0 f32 [n0,1], feats_1, matches int64 [M,2],
+        trans float64 [4,4] numpy): the 8-tuple of :820-822, device tensors but for trans."""
+    key = [apg._f32(xyz_0), apg._f32(xyz_1)]
+    M2 = np.array(M2, dtype=np.float64)
+    if random_rotation:
+        T0 = sample_random_trans(key[0], randg, np.pi / 4)
+        T1 = sample_random_trans(key[1], randg, np.pi / 4)
+        trans = T1 @ M2 @ np.linalg.inv(T0)
+        key = [apg.apply_transform(key[0], T0), apg.apply_transform(key[1], T1)]
+    else:
+        trans = M2
+    search = config.voxel_size * config.positive_pair_search_voxel_size_multiplier
+    if random_scale and pyrng.random() < 0.95:
+        scale = config.min_scale + (config.max_scale - config.min_scale) * pyrng.random()
+        search *= scale
+        key = [scale * key[0], scale * key[1]]
+        trans[:3, 3] = scale * trans[:3, 3]
+    sel = apg.voxel_first_rows(key, config.voxel_size)
+    xyz = [k[s].contiguous() for k, s in zip(key, sel)]
+    matches = apg.get_matching_indices(xyz[0], xyz[1], trans, search)
+    if len(matches) == 0:
+        matches = torch.tensor(NO_MATCH_FALLBACK, dtype=torch.int64, device=matches.device)
+    coords = [ops.voxelize(x, config.voxel_size, 0)[:, 1:].contiguous() for x in xyz]
+    feats = [torch.ones((len(x), 1), dtype=torch.float32, device=x.device) for x in xyz]
+    return (xyz[0], xyz[1], coords[0], coords[1], feats[0], feats[1], matches, trans)
+
+
+def _collate_pairs(list_data, concatenate):
+    xyz0, xyz1, coords0, coords1, feats0, feats1, matching_inds, trans = list(zip(*list_data))
+    xyz_batch0, xyz_batch1, matching_inds_batch, trans_batch, len_batch = [], [], [], [], []
+    as_tensor = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x))
+    start = np.zeros((1, 2), np.int64)
+    for b in range(len(coords0)):
+        N0, N1 = int(coords0[b].shape[0]), int(coords1[b].shape[0])
+        m = matching_inds[b]
+        m = m.cpu().numpy() if torch.is_tensor(m) else np.asarray(m)
+        if len(m) != 0:
+            xyz_batch0.append(as_tensor(xyz0[b]))
+            xyz_batch1.append(as_tensor(xyz1[b]))
+            trans_batch.append(as_tensor(trans[b]))
+            matching_inds_batch.append(torch.from_numpy(m.astype(np.int64).reshape(-1, 2) + start))
+            len_batch.append([N0, N1])
+        start[0, 0] += N0      # the head moves whether or not the item was kept
+        start[0, 1] += N1
+    coords_batch0, feats_batch0 = ME_utils.sparse_collate(coords0, feats0)
+    coords_batch1, feats_batch1 = ME_utils.sparse_collate(coords1, feats1)
+    return {
+        'pcd0': torch.cat(xyz_batch0, 0).float() if concatenate else xyz0,
+        'pcd1': torch.cat(xyz_batch1, 0).float() if concatenate else xyz1,
+        'sinput0_C': coords_batch0,
+        'sinput0_F': feats_batch0.float(),
+        'sinput1_C': coords_batch1,
+        'sinput1_F': feats_batch1.float(),
+        'correspondences': torch.cat(matching_inds_batch, 0).int(),
+        'T_gt': torch.cat(trans_batch, 0).float(),
+        'len_batch': len_batch,
+    }
+
+
+def collate_pair_fn(list_data):
+    """FCGF_APR/lib/data_loaders.py:26-78 on pair_sample's 8-tuples, same keys and dtypes: `pcd0` / `pcd1` are the KEPT
+    items' points concatenated (f32), everything else as collate_complement_pair_fn."""
+    return _collate_pairs(list_data, True)
+
+
+def collate_debug_pair_fn(list_data):
+    """:1282-1333: as collate_pair_fn, but `pcd0` / `pcd1` stay tuples of every item's tensor."""
+    return _collate_pairs(list_data, False)

@@ -648,6 +648,43 @@ int apr_contrastive_reduce(const float* pos_f0, const float* pos_f1, int32_t p, 
                            int32_t n_keys, int64_t hash_seed, float pos_thresh, float neg_thresh,
                            double* out6, void* stream);
 
+/* Pair-list losses: the arithmetic of the random-negative contrastive, triplet and hardest-triplet trainers, forward
+ *   and backward, with nothing read back by the host.  A loss is a list of n cross-cloud row pairs (r0[t], r1[t]) (i32;
+ *   a row outside its cloud gives a NaN distance and no gradient) over F0 f32[N0,c], F1 f32[N1,c] (c % 4 == 0, c <= 256,
+ *   16-byte aligned) and a table of terms over the pairs' distances. */
+#define APR_PAIR_MAX_GROUPS 4
+#define APR_PAIR_TERM_STAT 0      /* value d[pa], no gradient (a logged mean) */
+#define APR_PAIR_TERM_SQ 1        /* value d[pa] of a plain-square pair: the positive term of trainer.py:260 */
+#define APR_PAIR_TERM_NEG 2       /* value relu(margin - d[pb])^2: the negative term of trainer.py:263-264 */
+#define APR_PAIR_TERM_TRIPLET 3   /* value relu(d[pa] + margin - d[pb]): trainer.py:577, :724-729 */
+/* rows[i] = sel[best[i] & 0xffffffff] (-1 where that index is >= m): the D01ind = sel1[D01ind] step of
+ *   FCGF_APR/lib/trainer.py:698-699 on the packed apr_feature_nn result, without the copy to the host. */
+int apr_pair_rows_from_nn(const uint64_t* best, int64_t p, const int64_t* sel, int64_t m, int32_t* rows, void* stream);
+/* d[t] = |F0[r0[t]] - F1[r1[t]]|^2 for t < n_plain, sqrt(that + eps) for the rest, in the difference-square form of
+ *   FCGF_APR/lib/metrics.py:22-29 (as trainer.py:260, :264, :560, :574-575, :707, :721-722); coef[t] = 0, grp[t] = 0. */
+int apr_pair_dist(const float* F0, int64_t N0, const float* F1, int64_t N1, int32_t c, const int32_t* r0, const int32_t* r1,
+                  int64_t n, int64_t n_plain, float eps, float* d, float* coef, int32_t* grp, void* stream);
+/* The filter, hinge and means of FCGF_APR/lib/trainer.py:259-267, :568-579, :700-731.  terms i32[n_terms,4] =
+ *   (pa, pb, kp, kind | group << 8): pair indices (-1: none), kp = the pair whose key r0 + r1 * hash_seed drops the term
+ *   when it is among sorted_pos_keys (ascending i64; kp = -1: no filter).  Out: red f64[2 * n_groups] = {sum, count} of
+ *   the kept terms per group, summed in a fixed order (thread order inside a block, blocks ascending); mean f32[n_groups]
+ *   = sum / count, NaN for an empty group; coef[t] / grp[t] for every pair of a kept, active term of kind SQ / NEG /
+ *   TRIPLET: the factor of (F0[r0] - F1[r1]) in dF0 before the 1 / count, and the term's group -- a pair may stand in at
+ *   most one such term; kept u8[n_terms] (nullable). */
+size_t apr_pair_terms_scratch_bytes(int64_t n_terms);
+int apr_pair_terms_reduce(const float* d, const int32_t* r0, const int32_t* r1, int64_t n, const int32_t* terms,
+                          int64_t n_terms, const int64_t* sorted_pos_keys, int64_t n_keys, int64_t hash_seed, float margin,
+                          int32_t n_groups, double* red, float* mean, float* coef, int32_t* grp, uint8_t* kept,
+                          void* scratch, size_t scratch_bytes, void* stream);
+/* The backward of the index_select / boolean-index gathers under FCGF_APR/lib/trainer.py:271, :499, :626 without atomics:
+ *   dF0[r,:] = sum over t with r0[t] = r, in ascending t, of coef[t] * gout[grp[t]] / count[grp[t]] * (F0[r] - F1[r1[t]]),
+ *   dF1 mirrored; a row in no pair, or only in pairs with coef 0, gets exact zeros.  gout f32[n_gout]: the upstream
+ *   gradient of the first n_gout group means; red: as apr_pair_terms_reduce left it. */
+size_t apr_pair_grad_scratch_bytes(int64_t n, int64_t N0, int64_t N1);
+int apr_pair_grad(const float* F0, int64_t N0, const float* F1, int64_t N1, int32_t c, const int32_t* r0, const int32_t* r1,
+                  int64_t n, const float* coef, const int32_t* grp, const double* red, const float* gout, int32_t n_gout,
+                  float* dF0, float* dF1, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Point-set index builds of the KPConv encoder (Predator_APR)
  * ---------------------------------------------------------------------- */
