@@ -476,19 +476,13 @@ class _ConvBase(nn.Module):
             raise AprHipError("transposed convolution needs the encoder's coordinate map of that stride")
         return cm.kernel_map(ts, ts_out, self.kernel_size, self.stride != 1), ts_out
 
-    def _bf3_only(self, plist, cin, w_bf3):
-        """The launch reads the bf16-split image alone (weight-stationary / triple-list / output-stationary kernels at the
-        channel counts they cover): the tile pack need not exist."""
-        return plist is not None and w_bf3 is not None and cin in (64, 128, 192, 256, 384)
-
     def run_T(self, dout, nbr_bwd, n_in, flip, plist=None):
         """The input gradient: the same routed launch over the reverse map with the flipped-transposed kernel (channels
         swapped); `plist`: the reverse map's pair lists."""
         want_bf3 = plist is not None or nbr_bwd is None
         w_bf3 = self.packed_weight_T(flip, tile=False, bf3=True)[1] if want_bf3 else None
-        # the tile pack is built by ops.spconv only when the launch reads it (a K = 1 map on the dense kernels does not)
-        wp = None if self._bf3_only(plist, self.out_channels, w_bf3) else \
-            (lambda: self.packed_weight_T(flip, tile=True, bf3=False)[0])
+        # the tile pack is built by ops.spconv only when the routed kernel reads it (apr_spconv_route)
+        wp = lambda: self.packed_weight_T(flip, tile=True, bf3=False)[0]
         os_pairs = plist if isinstance(plist, ops.OsPairs) else None
         return ops.spconv(dout, nbr_bwd, self.kernel_volume if nbr_bwd is not None else 1, self.out_channels,
                           self.in_channels, wp, n_out=n_in, plist=None if os_pairs is not None else plist,
@@ -507,12 +501,9 @@ class _ConvBase(nn.Module):
             raise AprHipError("conv.run(l2norm=True) needs a SpconvBatch")
         w_bf3 = self.packed_weight_bf3() if (plist is not None or nbr is None) else None
         # a direct (un-batched) launch on a route that reads the split image alone does not need the tile pack: a training
-        # step re-packs every kernel once per optimizer step, so what is not read is not built (ops.spconv builds it on
-        # demand: the dense K = 1 kernels do not read it either)
-        if batch is None:
-            wp = None if self._bf3_only(plist, self.in_channels, w_bf3) else self.packed_weight
-        else:
-            wp = self.packed_weight()
+        # step re-packs every kernel once per optimizer step, so what is not read is not built (ops.spconv calls
+        # packed_weight on demand); a batch takes the tensor up front
+        wp = self.packed_weight if batch is None else self.packed_weight()
         return fn(feats, nbr, self.kernel_volume if nbr is not None else 1, self.in_channels,
                   self.out_channels, wp, scale=scale, shift=shift, residual=residual,
                   relu=relu, out=out, n_out=n_out, plist=None if os_pairs is not None else plist,

@@ -39,6 +39,10 @@ class SpconvDesc(C.Structure):
                 ("os_n_in", C.c_int64), ("l2norm", C.c_int32), ("ws3", C.c_int32)]
 
 
+# apr_spconv_route's ids (the APR_ROUTE_* enum of include/apr_hip.h)
+ROUTE_TILE, ROUTE_WS, ROUTE_WS_BF3, ROUTE_WS3, ROUTE_OS, ROUTE_DENSE_ROWS, ROUTE_DENSE_GEMM = range(7)
+
+
 class ResunetLayer(C.Structure):
     """struct apr_resunet_layer (include/apr_hip.h)."""
     _fields_ = [("K", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("relu", C.c_int32),
@@ -129,6 +133,8 @@ PROTOTYPES = {
     "apr_spconv_wgrad_scratch_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "apr_spconv_wgrad": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "apr_spconv_wgrad_same_level": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    "apr_spconv_route": (_i32, [_p]),
+    "apr_spconv_ws_supported": (_i32, [_i32, _i32, _i32]),
     "apr_spconv_fwd_batch": (C.c_int, [_p, _i32, _p]),
     "apr_spconv_fwd_batch_timed": (C.c_int, [_p, _i32, _p, _p]),
     "apr_bn_stats": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _sz, _p]),

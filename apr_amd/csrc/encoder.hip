@@ -17,8 +17,6 @@ namespace {
 
 constexpr int kLevels = 4, kStages = 7, kMaps = 10, kMaxLists = 24;
 
-inline bool ws_shape_ok(int K, int cin, int cout) { return K <= 27 && cin % 64 == 0 && cin <= 512 && cout % 64 == 0; }
-
 struct ListSlot {     // a pair list of one kernel map: kind 0 per-offset, 1 triples, 2 output-stationary tiles
   int map, kind, rows;
   void* blob;
@@ -174,7 +172,7 @@ struct Enc {
     return prod;
   }
 
-  // one conv launch (SpconvBatch.add in apr_amd/ops.py, the same routing)
+  // one conv launch: the descriptor gets what the stage has for the layer, apr_spconv_route picks the family from it
   void conv(const apr_resunet_layer& L, const float* in, int64_t ldi, int m, int64_t n_out, ListSlot* list, const float* residual,
             int64_t ldr, float* out, int64_t ldo, bool l2norm) {
     if (!ok()) return;
@@ -193,7 +191,7 @@ struct Enc {
         d.os_build_bytes = (int64_t)list->bytes;
         list->built = true;
       }
-    } else if (list && list->kind != 2 && m >= 0 && ws_shape_ok(L.K, L.cin, L.cout)) {
+    } else if (list && list->kind != 2 && m >= 0 && apr_spconv_ws_supported(L.K, L.cin, L.cout)) {
       const bool is3 = list->kind == 1;
       d.prod_scratch = prod_rows((size_t)n_out * (is3 ? 9 : 27) * L.cout);
       d.counters = list->counters; d.plist = list->blob; d.ws3 = is3 ? 1 : 0;
@@ -202,11 +200,8 @@ struct Enc {
         d.plist_bytes = (int64_t)list->bytes;
         list->built = true;
       }
-    } else if (m < 0 && L.K == 1 && L.w_bf3 && ((L.cin % 64 == 0 && L.cout % 64 == 0) || apr_dense_rows_bf3_ok(L.cin, L.cout)) &&
-               ldi % 4 == 0 && ldo % 4 == 0 &&
-               (dry || (((uintptr_t)in | (uintptr_t)out) % 16 == 0 && (!residual || (ldr % 4 == 0 && (uintptr_t)residual % 16 == 0)) &&
-                        (!L.scale || (uintptr_t)L.scale % 16 == 0) && (!L.shift || (uintptr_t)L.shift % 16 == 0)))) {
-      d.w_bf3 = L.w_bf3;          // identity map: the dense GEMMs on the bf16 split (dense.hip / dense_rows.hip)
+    } else if (m < 0 && L.K == 1 && L.w_bf3) {
+      d.w_bf3 = L.w_bf3;          // identity map: the dense kernels on the bf16 split where apr_spconv_route finds them fit
     }
     if (!dry) descs[ndesc++] = d;
   }
@@ -267,12 +262,12 @@ struct Enc {
           run(apr_occ_conv(lv[0].coords, n_out, bbox, P.conv1_ks, P.conv1_w, C.cout, C.scale, C.shift, nullptr, 0, C.relu, A,
                            C.cout, occ, occ_bytes + 256, st));
       } else {
-        ListSlot* cl = ((P.ws_conv >> s) & 1u) && ws_shape_ok(C.K, C.cin, C.cout) ? ws_list(C, q.cmap, false) : nullptr;
+        ListSlot* cl = ((P.ws_conv >> s) & 1u) && apr_spconv_ws_supported(C.K, C.cin, C.cout) ? ws_list(C, q.cmap, false) : nullptr;
         conv(C, q.in, q.ldi, q.cmap, n_out, cl, nullptr, 0, A, C.cout, false);
       }
       ListSlot* bl = nullptr;
       if (((P.os_block >> s) & 1u) && B1.cin == 64 && B1.w_bf3 && n_out >= P.os_min_rows) bl = os_list(B1, q.bmap);
-      if (!bl && ((P.ws_block >> s) & 1u) && ws_shape_ok(B1.K, B1.cin, B1.cout)) bl = ws_list(B1, q.bmap, true);
+      if (!bl && ((P.ws_block >> s) & 1u) && apr_spconv_ws_supported(B1.K, B1.cin, B1.cout)) bl = ws_list(B1, q.bmap, true);
       conv(B1, A, B1.cin, q.bmap, n_out, bl, nullptr, 0, H, B1.cout, false);
       conv(B2, H, B2.cin, q.bmap, n_out, bl, A, B1.cin, q.out, q.ldo, false);
       flush();

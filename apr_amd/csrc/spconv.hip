@@ -508,30 +508,24 @@ inline bool use_mfma(int K, int cin, int cout) {
 }
 
 template <int TM, int CN, int WM, int WN, int CK>
-int launch_mfma(const float* in, int64_t ldi, const int* nbr, int64_t n_out, int K, int cin,
-                int cout, const float* wp, const float* scale, const float* shift,
-                const float* residual, int64_t ldr, int relu, float* out, int64_t ldo,
-                hipStream_t st) {
-  int64_t tiles = cdiv64(n_out, TM) * (cout / CN);
-  hipLaunchKernelGGL((k_spconv_mfma<TM, CN, WM, WN, CK>), dim3((unsigned)tiles), dim3(256), 0, st, in,
-                     ldi, nbr, (int)n_out, K, cin, cout, wp, scale, shift, residual, ldr, relu, out,
-                     ldo);
+int launch_mfma(const apr_spconv_desc& d, hipStream_t st) {
+  int64_t tiles = cdiv64(d.n_out, TM) * (d.cout / CN);
+  hipLaunchKernelGGL((k_spconv_mfma<TM, CN, WM, WN, CK>), dim3((unsigned)tiles), dim3(256), 0, st, d.in, d.ldi, d.nbr,
+                     (int)d.n_out, d.K, d.cin, d.cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }
 
 template <int TM, int CN, int CK, int NW>
-int launch_pairs(const float* in, int64_t ldi, const int* nbr, int64_t n_out, int K, int cin,
-                 int cout, const float* wp, const float* scale, const float* shift,
-                 const float* residual, int64_t ldr, int relu, float* out, int64_t ldo,
-                 hipStream_t st, int l2norm = 0) {
-  int64_t tiles = cdiv64(n_out, TM) * (cout / CN);
-  if (l2norm && cout != CN) {
-    apr_set_error("spconv: fused row normalisation needs the whole row in one tile (cout %d, tile %d)", cout, CN);
+int launch_pairs(const apr_spconv_desc& d, hipStream_t st, int l2norm = 0) {
+  int64_t tiles = cdiv64(d.n_out, TM) * (d.cout / CN);
+  if (l2norm && d.cout != CN) {
+    apr_set_error("spconv: fused row normalisation needs the whole row in one tile (cout %d, tile %d)", d.cout, CN);
     return APR_EINVAL;
   }
-  hipLaunchKernelGGL((k_spconv_pairs<TM, CN, CK, NW>), dim3((unsigned)tiles), dim3(64 * NW), 0, st, in, ldi,
-                     nbr, (int)n_out, K, cin, cout, wp, scale, shift, residual, ldr, relu, out, ldo, l2norm);
+  hipLaunchKernelGGL((k_spconv_pairs<TM, CN, CK, NW>), dim3((unsigned)tiles), dim3(64 * NW), 0, st, d.in, d.ldi, d.nbr,
+                     (int)d.n_out, d.K, d.cin, d.cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo,
+                     l2norm);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }
@@ -567,67 +561,33 @@ APR_API int apr_weights_flip_transpose(const float* w, int32_t K, int32_t cin, i
   return APR_OK;
 }
 
-// apr_spconv_fwd + optional row normalisation of the result (out[j] /= |out[j]|_2): fused into the tile kernel's
-// epilogue when that kernel runs the layer with the whole row in one tile (cout 32 or 64), else a second launch.
-static int spconv_fwd_impl(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K, int32_t cin,
-                           int32_t cout, const float* w_packed, const float* scale, const float* shift,
-                           const float* residual, int64_t ldr, int32_t relu, float* out, int64_t ldo, void* stream,
-                           int l2norm);
-
-APR_API int apr_spconv_fwd(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K,
-                           int32_t cin, int32_t cout, const float* w_packed, const float* scale,
-                           const float* shift, const float* residual, int64_t ldr, int32_t relu,
-                           float* out, int64_t ldo, void* stream) {
-  return spconv_fwd_impl(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift, residual, ldr, relu, out, ldo, stream, 0);
-}
-
-static int spconv_fwd_plain(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K, int32_t cin,
-                            int32_t cout, const float* w_packed, const float* scale, const float* shift,
-                            const float* residual, int64_t ldr, int32_t relu, float* out, int64_t ldo, void* stream,
-                            int l2f, bool* fused);
-
-static int spconv_fwd_impl(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K, int32_t cin,
-                           int32_t cout, const float* w_packed, const float* scale, const float* shift,
-                           const float* residual, int64_t ldr, int32_t relu, float* out, int64_t ldo, void* stream,
-                           int l2norm) {
-  bool fused = false;
-  int rc = spconv_fwd_plain(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift, residual, ldr, relu, out, ldo,
-                            stream, l2norm, &fused);
-  if (rc != APR_OK || !l2norm || fused || n_out == 0) return rc;
-  return apr_l2_normalize(out, ldo, n_out, cout, out, ldo, stream);
-}
-
-static int spconv_fwd_plain(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K, int32_t cin,
-                            int32_t cout, const float* w_packed, const float* scale, const float* shift,
-                            const float* residual, int64_t ldr, int32_t relu, float* out, int64_t ldo, void* stream,
-                            int l2f, bool* fused) {
-  hipStream_t st = (hipStream_t)stream;
+static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, bool* fused) {
+  const int64_t n_out = d.n_out;
+  const int K = d.K, cin = d.cin, cout = d.cout;
   APR_CHECK_ARG(n_out >= 0 && n_out < (1ll << 31), "apr_spconv_fwd: n_out=%lld", (long long)n_out);
   APR_CHECK_ARG(K >= 1 && cin >= 1 && cout >= 1, "apr_spconv_fwd: bad K/cin/cout");
-  APR_CHECK_ARG(nbr != nullptr || K == 1, "apr_spconv_fwd: identity map needs K == 1");
-  APR_CHECK_ARG(ldi >= cin && ldo >= cout, "apr_spconv_fwd: leading dimension smaller than channels");
-  APR_CHECK_ARG(!residual || ldr >= cout, "apr_spconv_fwd: ldr < cout");
+  APR_CHECK_ARG(d.nbr != nullptr || K == 1, "apr_spconv_fwd: identity map needs K == 1");
+  APR_CHECK_ARG(d.ldi >= cin && d.ldo >= cout, "apr_spconv_fwd: leading dimension smaller than channels");
+  APR_CHECK_ARG(!d.residual || d.ldr >= cout, "apr_spconv_fwd: ldr < cout");
   if (n_out == 0) return APR_OK;
   static const int s_impl = env_int("APR_SPCONV_IMPL", 2);      // 1 = dense-tile kernel, 2 = pair-compacted
   static const int s_tm = env_int("APR_SPCONV_TM", 0);           // 0 = heuristic
-  const bool vec_ok = (ldi % 4) == 0 && (((uintptr_t)in) & 15) == 0 && (ldo % 4) == 0 &&
-                      (((uintptr_t)out) & 15) == 0 &&
-                      (!residual || ((ldr % 4) == 0 && (((uintptr_t)residual) & 15) == 0));
+  const bool vec_ok = (d.ldi % 4) == 0 && (((uintptr_t)d.in) & 15) == 0 && (d.ldo % 4) == 0 &&
+                      (((uintptr_t)d.out) & 15) == 0 &&
+                      (!d.residual || ((d.ldr % 4) == 0 && (((uintptr_t)d.residual) & 15) == 0));
   // identity map (dense layer: K = 1 convolutions, Predator's Linear layers and KPConv's second step): dense.hip
-  if (nbr == nullptr && K == 1 && vec_ok && apr_internal_dense_ok(n_out, cin, cout) &&
-      ((((uintptr_t)scale) | ((uintptr_t)shift) | ((uintptr_t)w_packed)) & 15) == 0)
-    return apr_internal_dense_gemm(in, ldi, n_out, cin, cout, w_packed, scale, shift, residual, ldr, relu, out, ldo, st);
+  if (d.nbr == nullptr && K == 1 && vec_ok && apr_internal_dense_ok(n_out, cin, cout) &&
+      ((((uintptr_t)d.scale) | ((uintptr_t)d.shift) | ((uintptr_t)d.w_packed)) & 15) == 0)
+    return apr_internal_dense_gemm(d.in, d.ldi, n_out, cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu,
+                                   d.out, d.ldo, st);
   if (s_impl == 2 && use_mfma(K, cin, cout) && K <= kKMax && vec_ok) {
     // the row normalisation rides in this kernel's epilogue when a tile holds the whole row (CN == cout)
     const int l2k = (l2f && (cout == 32 || cout == 64)) ? 1 : 0;
     static const int s_nw = env_int("APR_SPCONV_NW", 4);
     if (l2k && !(s_nw == 8 && cout % 64 == 0) && !(cout == 64 && env_int("APR_SPCONV_CN", 0) == 32)) *fused = true;
-#define APR_PAIRS(TM_, CN_, CK_)                                                                      \
-  return launch_pairs<TM_, CN_, CK_, 4>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,    \
-                                        residual, ldr, relu, out, ldo, st, *fused ? 1 : 0)
+#define APR_PAIRS(TM_, CN_, CK_) return launch_pairs<TM_, CN_, CK_, 4>(d, st, *fused ? 1 : 0)
     if (s_nw == 8 && cout % 64 == 0)   // 8-wave tiles: 32-row tile, 32-channel pieces (<= 128 VGPRs, 4 waves/SIMD)
-      return launch_pairs<32, 64, 32, 8>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift, residual, ldr,
-                                         relu, out, ldo, st);
+      return launch_pairs<32, 64, 32, 8>(d, st);
     static const int s_ck = env_int("APR_SPCONV_CK", 0);
     static const int s_cn = env_int("APR_SPCONV_CN", 0);
     const bool cn64 = (cout % 64 == 0) && s_cn != 32;
@@ -656,111 +616,129 @@ static int spconv_fwd_plain(const float* in, int64_t ldi, const int32_t* nbr, in
     APR_PAIRS(32, 32, 32);
 #undef APR_PAIRS
   }
-  if (use_mfma(K, cin, cout) && (ldi % 4) == 0 && (((uintptr_t)in) & 15) == 0) {
-    const bool big = n_out >= 32768;
-    if (cout % 64 == 0) {
-      if (cin % 64 == 0) {
-        if (big)
-          return launch_mfma<64, 64, 1, 4, 64>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                               residual, ldr, relu, out, ldo, st);
-        return launch_mfma<32, 64, 1, 4, 64>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                             residual, ldr, relu, out, ldo, st);
-      }
-      if (big)
-        return launch_mfma<64, 64, 1, 4, 32>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                             residual, ldr, relu, out, ldo, st);
-      return launch_mfma<32, 64, 1, 4, 32>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                           residual, ldr, relu, out, ldo, st);
-    }
-    if (cin % 64 == 0) {
-      if (big)
-        return launch_mfma<64, 32, 2, 2, 64>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                             residual, ldr, relu, out, ldo, st);
-      return launch_mfma<32, 32, 2, 2, 64>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                           residual, ldr, relu, out, ldo, st);
-    }
-    if (big)
-      return launch_mfma<64, 32, 2, 2, 32>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                           residual, ldr, relu, out, ldo, st);
-    return launch_mfma<32, 32, 2, 2, 32>(in, ldi, nbr, n_out, K, cin, cout, w_packed, scale, shift,
-                                         residual, ldr, relu, out, ldo, st);
+  if (use_mfma(K, cin, cout) && (d.ldi % 4) == 0 && (((uintptr_t)d.in) & 15) == 0) {
+#define APR_MFMA(CN_, WM_, WN_, CK_) \
+  return big ? launch_mfma<64, CN_, WM_, WN_, CK_>(d, st) : launch_mfma<32, CN_, WM_, WN_, CK_>(d, st)
+    const bool big = n_out >= 32768, cn64 = cout % 64 == 0, ck64 = cin % 64 == 0;
+    if (cn64 && ck64) APR_MFMA(64, 1, 4, 64);
+    if (cn64) APR_MFMA(64, 1, 4, 32);
+    if (ck64) APR_MFMA(32, 2, 2, 64);
+    APR_MFMA(32, 2, 2, 32);
+#undef APR_MFMA
   }
   APR_CHECK_ARG(!use_mfma(K, cin, cout),
                 "apr_spconv_fwd: MFMA-shaped layer needs 16-B aligned input rows (ldi %% 4 == 0)");
-  if (nbr && (cin == 1 || cin == 3) && cout % 32 == 0 && (size_t)64 * K * 4 <= 64 * 1024 &&
-      (((uintptr_t)w_packed) & 15) == 0) {
+  if (d.nbr && (cin == 1 || cin == 3) && cout % 32 == 0 && (size_t)64 * K * 4 <= 64 * 1024 &&
+      (((uintptr_t)d.w_packed) & 15) == 0) {
     const unsigned grid = (unsigned)cdiv64(n_out, 64);
     const size_t lds = (size_t)64 * K * 4;
     if (cin == 1)
-      hipLaunchKernelGGL(k_spconv_smallcin<1>, dim3(grid), dim3(256), lds, st, in, ldi, nbr, (int)n_out, K, cout,
-                         w_packed, scale, shift, residual, ldr, relu, out, ldo);
+      hipLaunchKernelGGL(k_spconv_smallcin<1>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
+                         d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
     else
-      hipLaunchKernelGGL(k_spconv_smallcin<3>, dim3(grid), dim3(256), lds, st, in, ldi, nbr, (int)n_out, K, cout,
-                         w_packed, scale, shift, residual, ldr, relu, out, ldo);
+      hipLaunchKernelGGL(k_spconv_smallcin<3>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
+                         d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
     APR_LAUNCH_CHECK();
     return APR_OK;
   }
   int64_t total = n_out * cout;
-  hipLaunchKernelGGL(k_spconv_generic, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, in, ldi, nbr,
-                     n_out, K, cin, cout, w_packed, scale, shift, residual, ldr, relu, out, ldo);
+  hipLaunchKernelGGL(k_spconv_generic, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, d.in, d.ldi, d.nbr, n_out, K,
+                     cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
   APR_LAUNCH_CHECK();
   return APR_OK;
 }
 
+// apr_spconv_fwd + optional row normalisation of the result (out[j] /= |out[j]|_2): fused into the tile kernel's
+// epilogue when that kernel runs the layer with the whole row in one tile (cout 32 or 64), else a second launch.
+static int spconv_fwd_impl(const apr_spconv_desc& d, hipStream_t st, int l2norm) {
+  bool fused = false;
+  int rc = spconv_fwd_plain(d, st, l2norm, &fused);
+  if (rc != APR_OK || !l2norm || fused || d.n_out == 0) return rc;
+  return apr_l2_normalize(d.out, d.ldo, d.n_out, d.cout, d.out, d.ldo, st);
+}
+
+APR_API int apr_spconv_fwd(const float* in, int64_t ldi, const int32_t* nbr, int64_t n_out, int32_t K,
+                           int32_t cin, int32_t cout, const float* w_packed, const float* scale,
+                           const float* shift, const float* residual, int64_t ldr, int32_t relu,
+                           float* out, int64_t ldo, void* stream) {
+  apr_spconv_desc d = {};
+  d.in = in; d.ldi = ldi; d.nbr = nbr; d.n_out = n_out;
+  d.K = K; d.cin = cin; d.cout = cout; d.relu = relu;
+  d.w_packed = w_packed; d.scale = scale; d.shift = shift;
+  d.residual = residual; d.ldr = ldr;
+  d.out = out; d.ldo = ldo;
+  return spconv_fwd_impl(d, (hipStream_t)stream, 0);
+}
+
+// The 16-byte rows and vectors that the K = 1 kernels on the split weights (dense.hip, dense_rows.hip) ask for
+static bool dense_bf3_aligned(const apr_spconv_desc& d) {
+  return d.ldi % 4 == 0 && d.ldo % 4 == 0 &&
+         ((((uintptr_t)d.in) | ((uintptr_t)d.out) | ((uintptr_t)d.scale) | ((uintptr_t)d.shift)) & 15) == 0 &&
+         (!d.residual || (d.ldr % 4 == 0 && (((uintptr_t)d.residual) & 15) == 0));
+}
+
+// The routing rule ("How a conv layer is routed"): host arithmetic on the descriptor, w_packed not looked at.
+APR_API int32_t apr_spconv_route(const apr_spconv_desc* dp) {
+  APR_CHECK_ARG(dp != nullptr, "apr_spconv_route: null descriptor");
+  const apr_spconv_desc& d = *dp;
+  if (d.os_pairs && d.w_bf3 && d.nbr) return APR_ROUTE_OS;
+  if (d.plist && d.nbr && apr_spconv_ws_supported(d.K, d.cin, d.cout)) {
+    if (!d.ws3) return apr_internal_ws_bf3_only(d.w_bf3, d.cin) ? APR_ROUTE_WS_BF3 : APR_ROUTE_WS;
+    APR_CHECK_ARG(d.w_bf3 && apr_spconv_ws3_supported(d.K, d.cin, d.cout),
+                  "spconv: triple pair lists need the bf16-split weights and cin 64 / 128, K = 27");
+    return APR_ROUTE_WS3;
+  }
+  if (!d.nbr && d.K == 1 && d.w_bf3 && dense_bf3_aligned(d)) {
+    // few input channels over many rows (conv1_tr / final on the finest level, resunet.py:126-140): the weight-resident row
+    // stream; other 64-multiple widths (the wide variants' conv1_tr / final, resunet.py:224-251): the tiled GEMM, 1.5-1.7x
+    // the exact-fp32 MFMA kernel
+    if (apr_internal_dense_rows_route(d.n_out, d.cin, d.cout)) return APR_ROUTE_DENSE_ROWS;
+    if (d.cin % 64 == 0 && d.cout % 64 == 0 && d.n_out > 0) return APR_ROUTE_DENSE_GEMM;
+  }
+  return APR_ROUTE_TILE;
+}
+
 static int spconv_batch_one(const apr_spconv_desc& d, void* stream, hipEvent_t e0, hipEvent_t e1) {
   hipStream_t st = (hipStream_t)stream;
-  bool dense_bf3 = false, rows_bf3 = false;
-  if (d.os_pairs && d.w_bf3) {   // output-stationary path (spconv_os.hip): tile lists built on first use of the map
-    if (d.os_build_bytes > 0) {
-      int rcb = apr_spconv_os_pairs_build(d.nbr, d.n_out, d.os_n_in, d.K, (int32_t)d.os_rows, d.os_pairs,
-                                          (size_t)d.os_build_bytes, stream);
-      if (rcb != APR_OK) return rcb;
-    }
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rco = apr_spconv_os_fwd(d.in, d.ldi, d.os_pairs, d.n_out, d.K, (int32_t)d.os_rows, d.cin, d.cout, d.w_bf3, d.scale,
-                                d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo, stream);
-    if (rco != APR_OK) return rco;
-  } else if (d.plist && d.ws3 && d.w_bf3) {   // triple pair lists: half the product rows (spconv_ws.hip)
-    if (d.plist_bytes > 0) {
-      int rcb = apr_pairlist3_build(d.nbr, d.n_out, d.K, d.counters, d.plist, (size_t)d.plist_bytes, stream);
-      if (rcb != APR_OK) return rcb;
-    }
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rcw = apr_spconv_ws3_fwd_bf3(d.in, d.ldi, d.counters, d.plist, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift,
-                                     d.residual, d.ldr, d.relu, d.out, d.ldo, d.prod_scratch, stream);
-    if (rcw != APR_OK) return rcw;
-  } else if (d.plist) {
-    if (d.plist_bytes > 0) {   // the pair-list build is per map, not part of the timed conv layer
-      int rcb = apr_pairlist_build(d.nbr, d.n_out, d.K, d.counters, d.plist, (size_t)d.plist_bytes, stream);
-      if (rcb != APR_OK) return rcb;
-    }
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rcw = apr_spconv_ws_fwd_bf3(d.in, d.ldi, d.counters, d.plist, d.n_out, d.K, d.cin, d.cout, d.w_packed, d.w_bf3,
-                                    d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo, d.prod_scratch, stream);
-    if (rcw != APR_OK) return rcw;
-  } else if (!d.nbr && d.K == 1 && d.w_bf3 && apr_internal_dense_rows_route(d.n_out, d.cin, d.cout)) {
-    // K = 1 layer with few input channels over many rows (conv1_tr / final on the finest level, resunet.py:126-140): the
-    // weight-resident row stream (dense_rows.hip), the row normalisation in its epilogue
-    rows_bf3 = true;
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rcd = apr_dense_rows_bf3(d.in, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift, d.residual, d.ldr, d.relu,
-                                 d.l2norm, d.out, d.ldo, stream);
-    if (rcd != APR_OK) return rcd;
-  } else if (!d.nbr && d.K == 1 && d.w_bf3 && d.cin % 64 == 0 && d.cout % 64 == 0 && d.n_out > 0) {
-    // K = 1 layer with 64-multiple widths and split weights (the wide variants' conv1_tr / final, resunet.py:224-251): the
-    // dense GEMM on the bf16 split (dense.hip), 1.5-1.7x the exact-fp32 MFMA kernel
-    dense_bf3 = true;
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rcd = apr_dense_gemm_bf3(d.in, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift, d.residual, d.ldr, d.relu,
-                                 d.out, d.ldo, stream);
-    if (rcd != APR_OK) return rcd;
-  } else {
-    if (e0) APR_HIP(hipEventRecord(e0, st));
-    int rc = spconv_fwd_impl(d.in, d.ldi, d.nbr, d.n_out, d.K, d.cin, d.cout, d.w_packed, d.scale, d.shift, d.residual,
-                             d.ldr, d.relu, d.out, d.ldo, stream, d.l2norm);
-    if (rc != APR_OK) return rc;
+  const int32_t route = apr_spconv_route(&d);
+  if (route < 0) return route;
+  int rc = APR_OK;
+  // a list is built on the first use of its map; the build is per map, not part of the timed conv layer
+  if (route == APR_ROUTE_OS && d.os_build_bytes > 0)
+    rc = apr_spconv_os_pairs_build(d.nbr, d.n_out, d.os_n_in, d.K, (int32_t)d.os_rows, d.os_pairs, (size_t)d.os_build_bytes, stream);
+  else if (route == APR_ROUTE_WS3 && d.plist_bytes > 0)
+    rc = apr_pairlist3_build(d.nbr, d.n_out, d.K, d.counters, d.plist, (size_t)d.plist_bytes, stream);
+  else if ((route == APR_ROUTE_WS || route == APR_ROUTE_WS_BF3) && d.plist_bytes > 0)
+    rc = apr_pairlist_build(d.nbr, d.n_out, d.K, d.counters, d.plist, (size_t)d.plist_bytes, stream);
+  if (rc != APR_OK) return rc;
+  if (e0) APR_HIP(hipEventRecord(e0, st));
+  switch (route) {
+    case APR_ROUTE_OS:
+      rc = apr_spconv_os_fwd(d.in, d.ldi, d.os_pairs, d.n_out, d.K, (int32_t)d.os_rows, d.cin, d.cout, d.w_bf3, d.scale, d.shift,
+                             d.residual, d.ldr, d.relu, d.out, d.ldo, stream);
+      break;
+    case APR_ROUTE_WS3:
+      rc = apr_spconv_ws3_fwd_bf3(d.in, d.ldi, d.counters, d.plist, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift, d.residual,
+                                  d.ldr, d.relu, d.out, d.ldo, d.prod_scratch, stream);
+      break;
+    case APR_ROUTE_WS:
+    case APR_ROUTE_WS_BF3:
+      rc = apr_spconv_ws_fwd_bf3(d.in, d.ldi, d.counters, d.plist, d.n_out, d.K, d.cin, d.cout, d.w_packed, d.w_bf3, d.scale,
+                                 d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo, d.prod_scratch, stream);
+      break;
+    case APR_ROUTE_DENSE_ROWS:      // the row normalisation in its epilogue
+      rc = apr_dense_rows_bf3(d.in, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift, d.residual, d.ldr, d.relu, d.l2norm,
+                              d.out, d.ldo, stream);
+      break;
+    case APR_ROUTE_DENSE_GEMM:
+      rc = apr_dense_gemm_bf3(d.in, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out,
+                              d.ldo, stream);
+      break;
+    default:      // APR_ROUTE_TILE: normalises in its own epilogue or by its own second launch
+      rc = spconv_fwd_impl(d, st, d.l2norm);
   }
-  if (d.l2norm && !rows_bf3 && (d.plist || (d.os_pairs && d.w_bf3) || dense_bf3) && d.n_out > 0) {   // other conv families: a second launch
+  if (rc != APR_OK) return rc;
+  if (d.l2norm && route != APR_ROUTE_TILE && route != APR_ROUTE_DENSE_ROWS && d.n_out > 0) {   // other families: a second launch
     int rcn = apr_l2_normalize(d.out, d.ldo, d.n_out, d.cout, d.out, d.ldo, stream);
     if (rcn != APR_OK) return rcn;
   }

@@ -832,14 +832,26 @@ APR_API int apr_pairlist_build(const int32_t* nbr, int64_t n_out, int32_t K, int
   return APR_OK;
 }
 
+// The one shape predicate of the weight-stationary families (pair and triple lists); the router, the encoder's walk and the
+// Python binding all ask here.
+APR_API int32_t apr_spconv_ws_supported(int32_t K, int32_t cin, int32_t cout) {
+  return K >= 1 && K <= 27 && cin > 0 && cin % 64 == 0 && cin <= 512 && cout > 0 && cout % 64 == 0;
+}
+
+// Whether ws_fwd runs the layer on the split weights alone (k_ws_gemm_bf3's instantiated widths): then w_packed is not read.
+// 192 / 384 input channels: the transposed convolutions behind a skip concatenation in the wide variants (ResUNetFatBN:
+// conv2_tr 192 -> 128, conv3_tr 384 -> 128, FCGF_APR/model/resunet.py:224-227) -- same kernel, 3 / 6 chunks per group
+bool apr_internal_ws_bf3_only(const void* w_bf3, int32_t cin) {
+  return w_bf3 && (cin == 64 || cin == 128 || cin == 192 || cin == 256 || cin == 384);
+}
+
 static int ws_fwd(const float* in, int64_t ldi, const int32_t* counters, const void* plist, int64_t n_out, int32_t K,
                   int32_t cin, int32_t cout, const float* w_packed, const void* w_bf3, const float* scale,
                   const float* shift, const float* residual, int64_t ldr, int32_t relu, float* out, int64_t ldo,
                   float* prod_scratch, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(n_out > 0 && n_out < (1ll << 31) / 32 && K >= 1 && K <= 27, "apr_spconv_ws_fwd: bad n_out / K");
-  APR_CHECK_ARG(cin % 64 == 0 && cin <= 512 && cout % 64 == 0,
-                "apr_spconv_ws_fwd: needs cin %% 64 == 0, cin <= 512 and cout %% 64 == 0");
+  APR_CHECK_ARG(apr_spconv_ws_supported(K, cin, cout), "apr_spconv_ws_fwd: needs cin %% 64 == 0, cin <= 512 and cout %% 64 == 0");
   APR_CHECK_ARG(ldi > 0 && ldi < (1ll << 31), "apr_spconv_ws_fwd: ldi out of range");
   APR_CHECK_ARG(ldi % 4 == 0 && ldo % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out) | ((uintptr_t)prod_scratch)) & 15) == 0,
                 "apr_spconv_ws_fwd: 16-byte aligned rows required");
@@ -880,9 +892,7 @@ static int ws_fwd(const float* in, int64_t ldi, const int32_t* counters, const v
       s_attr[dev] = true;
     }
   }
-  // 192 / 384 input channels: the transposed convolutions behind a skip concatenation in the wide variants (ResUNetFatBN:
-  // conv2_tr 192 -> 128, conv3_tr 384 -> 128, FCGF_APR/model/resunet.py:224-227) -- same kernel, 3 / 6 chunks per group
-  if (w_bf3 && (cin == 64 || cin == 128 || cin == 192 || cin == 256 || cin == 384)) {
+  if (apr_internal_ws_bf3_only(w_bf3, cin)) {
     // bf16 3-way split path: slice = cin * 64 * 6 B
     const size_t lds3 = (size_t)cin * 64 * 6;
     int64_t per_cu3 = (160 * 1024) / (int64_t)lds3;

@@ -658,25 +658,24 @@ def spconv_os(x, os_pairs, cin, cout, w_bf3, scale=None, shift=None, residual=No
 
 
 def ws_supported(K, cin, cout):
-    return K <= 27 and cin % 64 == 0 and cin <= 512 and cout % 64 == 0
+    return bool(_lib_().apr_spconv_ws_supported(int(K), int(cin), int(cout)))
 
 
-def spconv(x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu=False, out=None, n_out=None,
-           plist=None, w_bf3=None, os_pairs=None):
-    """out[j] = act((sum_o x[nbr[j,o]] @ W[o]) * scale + shift + residual[j]).
+_WS_ROUTES = (_lib.ROUTE_WS, _lib.ROUTE_WS_BF3, _lib.ROUTE_WS3)
+_PACK_ROUTES = (_lib.ROUTE_TILE, _lib.ROUTE_WS)      # the families whose kernels read the tile pack
 
-    x / residual / out may be column slices of wider row-major buffers.  With `plist` (the PairList of `nbr`)
-    the launch takes the weight-stationary path (apr_spconv_ws_fwd); with `os_pairs` (the OsPairs of `nbr`) and the
-    split weights the output-stationary one (apr_spconv_os_fwd).  `wp` may be a callable that returns the tile pack: it is
-    called only when the chosen kernel reads that pack.
-    """
-    if os_pairs is not None and w_bf3 is not None and nbr is not None:
-        return spconv_os(x, os_pairs, cin, cout, w_bf3, scale=scale, shift=shift, residual=residual, relu=relu, out=out)
+
+def _spconv_desc(x, nbr, K, cin, cout, wp, scale, shift, residual, relu, out, n_out, plist, w_bf3, os_pairs, prod_pool):
+    """The one filler of apr_spconv_desc, for spconv() and SpconvBatch.add(): checks the operands, hands the library what the
+    caller has for the layer and lets apr_spconv_route pick the kernel family -- no routing rule is restated here.  What
+    depends on the route follows it: the tile pack (a callable `wp` is called only where the kernels read the pack), the
+    product buffer (shared by size through `prod_pool`) and the list that the launch needs built.
+    -> (desc, route, out, list or None, tensors to keep alive)."""
     x, ldi = _rows(x, "spconv.x")
     if x.shape[1] != cin:
         raise _lib.AprHipError(f"spconv: input has {x.shape[1]} channels, weight expects {cin}")
     if nbr is not None:
-        if nbr.dtype != torch.int32 or not nbr.is_contiguous() or nbr.shape[1] != K:
+        if nbr.dtype != torch.int32 or not nbr.is_contiguous() or nbr.dim() != 2 or nbr.shape[1] != K:
             raise _lib.AprHipError("spconv: nbr must be a contiguous int32 [n_out, K] tensor")
         n_out = nbr.shape[0]
     elif n_out is None:
@@ -691,51 +690,91 @@ def spconv(x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu
         residual, ldr = _rows(residual, "spconv.residual")
         if residual.shape[0] != n_out or residual.shape[1] != cout:
             raise _lib.AprHipError("spconv: residual shape mismatch")
-    if (nbr is None and K == 1 and w_bf3 is not None and PROFILE is None and n_out > 0 and ldi % 4 == 0
-            and ldo % 4 == 0 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
-            and (residual is None or (ldr % 4 == 0 and residual.data_ptr() % 16 == 0))
-            and (scale is None or scale.data_ptr() % 16 == 0) and (shift is None or shift.data_ptr() % 16 == 0)):
-        # identity map: the dense GEMMs on the bf16 split (what a batched launch picks as well) -- few input channels over
-        # many rows stream past LDS-resident weights, the other 64-multiple widths take the tiled kernel
-        lib = _lib_()
-        if lib.apr_dense_rows_bf3_route(n_out, cin, cout):
-            check(lib.apr_dense_rows_bf3(ptr(x), ldi, n_out, cin, cout, ptr(w_bf3), ptr(scale), ptr(shift), ptr(residual), ldr,
-                                         int(bool(relu)), 0, ptr(out), ldo, stream()))
-            return out
-        if cin % 64 == 0 and cout % 64 == 0:
-            check(lib.apr_dense_gemm_bf3(ptr(x), ldi, n_out, cin, cout, ptr(w_bf3), ptr(scale), ptr(shift), ptr(residual), ldr,
-                                         int(bool(relu)), ptr(out), ldo, stream()))
-            return out
+    d = _lib.SpconvDesc()
+    d.inp, d.ldi, d.nbr, d.n_out = ptr(x), ldi, ptr(nbr), n_out
+    d.K, d.cin, d.cout, d.relu = K, cin, cout, int(bool(relu))
+    d.scale, d.shift, d.residual, d.ldr, d.out, d.ldo = ptr(scale), ptr(shift), ptr(residual), ldr, ptr(out), ldo
+    d.w_bf3 = ptr(w_bf3)
+    if plist is not None:
+        d.counters, d.plist, d.ws3 = ptr(plist.counters), ptr(plist.blob), int(isinstance(plist, PairList3))
+    if os_pairs is not None:
+        d.os_pairs, d.os_rows, d.os_n_in = ptr(os_pairs.blob), os_pairs.R, os_pairs.n_in
+    route = _lib_().apr_spconv_route(C.byref(d))
+    if route < 0:
+        check(route)
+    lst = os_pairs if route == _lib.ROUTE_OS else plist if route in _WS_ROUTES else None
+    if lst is not None and (lst.n_out != n_out or lst.K != K):
+        raise _lib.AprHipError("spconv: tile pair lists do not belong to this kernel map" if lst is os_pairs else
+                               "spconv: pair list does not belong to this kernel map")
     if callable(wp):
-        wp = wp()
-    use_ws = plist is not None and nbr is not None and ws_supported(K, cin, cout)
-    use_ws3 = use_ws and isinstance(plist, PairList3)
-    if use_ws3 and (w_bf3 is None or not ws3_supported(K, cin, cout)):
-        raise _lib.AprHipError("spconv: triple pair lists need the bf16-split weights and cin 64 / 128, K = 27")
-    if use_ws:
-        if plist.n_out != n_out or plist.K != K:
-            raise _lib.AprHipError("spconv: pair list does not belong to this kernel map")
-        prod = plist.build().prod_scratch(cout)
+        wp = wp() if route in _PACK_ROUTES else None
+    if wp is None and route in _PACK_ROUTES:
+        raise _lib.AprHipError("spconv: the routed kernel reads the tile pack (pack_weights) and none was given")
+    d.w_packed = ptr(wp)
+    prod = None
+    if route in _WS_ROUTES:      # launches run in order on one stream: a batch shares the scratch
+        need = n_out * (9 if d.ws3 else K) * cout
+        prod = prod_pool.get(need)
+        if prod is None:
+            prod = prod_pool[need] = plist.prod_scratch(cout)
+        d.prod_scratch = ptr(prod)
+    return d, route, out, lst, [x, nbr, wp, scale, shift, residual, out, plist, prod, w_bf3, os_pairs]
+
+
+def _route_label(route):
+    """SpconvProfile's path name of a route."""
+    return "os" if route == _lib.ROUTE_OS else "ws" if route in _WS_ROUTES else "tile"
+
+
+def _launch_routed(lib, route, d, st):
+    """One filled descriptor through the entry point of its route: what apr_spconv_fwd_batch does with it, called by name
+    from here so that an eager launch shows up as its family's own library call (the training tests tell the routes apart
+    by that name) and is timed by the caller's own events."""
+    epi = (d.scale, d.shift, d.residual, d.ldr, d.relu)
+    if route == _lib.ROUTE_OS:
+        return lib.apr_spconv_os_fwd(d.inp, d.ldi, d.os_pairs, d.n_out, d.K, d.os_rows, d.cin, d.cout, d.w_bf3, *epi, d.out, d.ldo, st)
+    if route == _lib.ROUTE_WS3:
+        return lib.apr_spconv_ws3_fwd_bf3(d.inp, d.ldi, d.counters, d.plist, d.n_out, d.cin, d.cout, d.w_bf3, *epi, d.out, d.ldo,
+                                          d.prod_scratch, st)
+    if route in _WS_ROUTES:
+        return lib.apr_spconv_ws_fwd_bf3(d.inp, d.ldi, d.counters, d.plist, d.n_out, d.K, d.cin, d.cout, d.w_packed, d.w_bf3, *epi,
+                                         d.out, d.ldo, d.prod_scratch, st)
+    if route == _lib.ROUTE_DENSE_ROWS:
+        return lib.apr_dense_rows_bf3(d.inp, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, *epi, 0, d.out, d.ldo, st)
+    if route == _lib.ROUTE_DENSE_GEMM:
+        return lib.apr_dense_gemm_bf3(d.inp, d.ldi, d.n_out, d.cin, d.cout, d.w_bf3, *epi, d.out, d.ldo, st)
+    return lib.apr_spconv_fwd(d.inp, d.ldi, d.nbr, d.n_out, d.K, d.cin, d.cout, d.w_packed, *epi, d.out, d.ldo, st)
+
+
+def spconv(x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu=False, out=None, n_out=None,
+           plist=None, w_bf3=None, os_pairs=None):
+    """out[j] = act((sum_o x[nbr[j,o]] @ W[o]) * scale + shift + residual[j]).
+
+    x / residual / out may be column slices of wider row-major buffers.  `plist` (the PairList of `nbr`), `os_pairs` (its
+    OsPairs) and `w_bf3` (the split weights) are what the caller has for the layer; the library picks the kernel family
+    from them (apr_spconv_route).  `wp` may be a callable that returns the tile pack: it is called only when the chosen
+    kernel reads that pack.
+    """
     prof = PROFILE
-    if prof is not None:
-        P = prof.pairs(nbr, n_out)
+    if prof is not None and nbr is None:      # the roofline leg times the K = 1 layers on the tile family
+        w_bf3 = None
+    d, route, out, lst, _keep = _spconv_desc(x, nbr, K, cin, cout, wp, scale, shift, residual, relu, out, n_out, plist, w_bf3,
+                                             os_pairs, {})
+    if lst is not None:
+        if lst.queued:
+            raise _lib.AprHipError("spconv: the pair lists of this map are queued for building in a SpconvBatch that has not "
+                                   "been launched yet")
+        lst.build()
+    if route == _lib.ROUTE_OS:      # as spconv_os(): not a profiled launch
+        prof = None
+    if prof is not None:      # a torch event pair, not the _timed entry point: that one synchronises
+        P = prof.pairs(nbr, d.n_out)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if use_ws3:
-        check(_lib_().apr_spconv_ws3_fwd_bf3(ptr(x), ldi, ptr(plist.counters), ptr(plist.blob), n_out, cin, cout, ptr(w_bf3),
-                                             ptr(scale), ptr(shift), ptr(residual), ldr, int(bool(relu)), ptr(out), ldo,
-                                             ptr(prod), stream()))
-    elif use_ws:
-        check(_lib_().apr_spconv_ws_fwd_bf3(ptr(x), ldi, ptr(plist.counters), ptr(plist.blob), n_out, K, cin, cout, ptr(wp),
-                                            ptr(w_bf3), ptr(scale), ptr(shift), ptr(residual), ldr, int(bool(relu)),
-                                            ptr(out), ldo, ptr(prod), stream()))
-    else:
-        check(_lib_().apr_spconv_fwd(ptr(x), ldi, ptr(nbr), n_out, K, cin, cout, ptr(wp), ptr(scale), ptr(shift),
-                                     ptr(residual), ldr, int(bool(relu)), ptr(out), ldo, stream()))
+    check(_launch_routed(_lib_(), route, d, stream()))
     if prof is not None:
         e1.record()
-        prof.records.append((P, cin, cout, K <= 32 and cin % 32 == 0 and cout % 32 == 0, e0, e1,
-                             "ws" if use_ws else "tile"))
+        prof.records.append((P, cin, cout, K <= 32 and cin % 32 == 0 and cout % 32 == 0, e0, e1, _route_label(route)))
     return out
 
 
@@ -1004,63 +1043,21 @@ class SpconvBatch:
 
     def add(self, x, nbr, K, cin, cout, wp, scale=None, shift=None, residual=None, relu=False, out=None, n_out=None,
             plist=None, w_bf3=None, os_pairs=None, l2norm=False):
-        x, ldi = _rows(x, "spconv.x")
-        if nbr is not None:
-            n_out = nbr.shape[0]
-        elif n_out is None:
-            n_out = x.shape[0]
-        if out is None:
-            out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-        out, ldo = _rows(out, "spconv.out")
-        ldr = 0
-        if residual is not None:
-            residual, ldr = _rows(residual, "spconv.residual")
-        d = _lib.SpconvDesc()
-        d.inp, d.ldi, d.nbr, d.n_out = x.data_ptr(), ldi, (nbr.data_ptr() if nbr is not None else None), n_out
-        d.K, d.cin, d.cout, d.relu = K, cin, cout, int(bool(relu))
+        d, route, out, lst, keep = _spconv_desc(x, nbr, K, cin, cout, wp, scale, shift, residual, relu, out, n_out, plist, w_bf3,
+                                                os_pairs, self.prod)
         d.l2norm = int(bool(l2norm))        # rows of the result divided by their 2-norm (fused where the kernel allows)
-        d.w_packed = wp.data_ptr()
-        d.scale = scale.data_ptr() if scale is not None else None
-        d.shift = shift.data_ptr() if shift is not None else None
-        d.residual = residual.data_ptr() if residual is not None else None
-        d.ldr, d.out, d.ldo = ldr, out.data_ptr(), ldo
-        prod = None
-        if os_pairs is not None and w_bf3 is not None and nbr is not None:
-            if os_pairs.n_out != n_out or os_pairs.K != K:
-                raise _lib.AprHipError("spconv: tile pair lists do not belong to this kernel map")
-            d.os_pairs, d.os_rows, d.os_n_in, d.w_bf3 = os_pairs.blob.data_ptr(), os_pairs.R, os_pairs.n_in, w_bf3.data_ptr()
-            if not os_pairs.built and not os_pairs.queued:      # built by this batch's launch; `built` is set there
-                d.os_build_bytes, os_pairs.queued = os_pairs.blob.numel(), True
-                self.pending.append(os_pairs)
-            plist = None
-        if plist is not None and nbr is not None and ws_supported(K, cin, cout):
-            if plist.n_out != n_out or plist.K != K:
-                raise _lib.AprHipError("spconv: pair list does not belong to this kernel map")
-            is3 = isinstance(plist, PairList3)
-            if is3 and (w_bf3 is None or not ws3_supported(K, cin, cout)):
-                raise _lib.AprHipError("spconv: triple pair lists need the bf16-split weights and cin 64 / 128, K = 27")
-            need = plist.n_out * (9 if is3 else plist.K) * cout      # launches run in order on one stream: share the scratch
-            prod = self.prod.get(need)
-            if prod is None:
-                prod = self.prod[need] = plist.prod_scratch(cout)
-            d.counters, d.plist, d.prod_scratch = plist.counters.data_ptr(), plist.blob.data_ptr(), prod.data_ptr()
-            d.ws3 = int(is3)
-            if w_bf3 is not None:
-                d.w_bf3 = w_bf3.data_ptr()
-            if not plist.built and not plist.queued:
-                d.plist_bytes, plist.queued = plist.blob.numel(), True
-                self.pending.append(plist)
-        elif nbr is None and K == 1 and w_bf3 is not None and ldi % 4 == 0 \
-                and ((cin % 64 == 0 and cout % 64 == 0) or _lib_().apr_dense_rows_bf3_ok(cin, cout)) \
-                and ldo % 4 == 0 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 \
-                and (residual is None or (ldr % 4 == 0 and residual.data_ptr() % 16 == 0)) \
-                and (scale is None or scale.data_ptr() % 16 == 0) and (shift is None or shift.data_ptr() % 16 == 0):
-            d.w_bf3 = w_bf3.data_ptr()          # identity map: the dense GEMMs on the bf16 split (the library routes by shape)
+        if lst is not None and not lst.built and not lst.queued:      # built by this batch's launch; `built` is set there
+            if route == _lib.ROUTE_OS:
+                d.os_build_bytes = lst.blob.numel()
+            else:
+                d.plist_bytes = lst.blob.numel()
+            lst.queued = True
+            self.pending.append(lst)
         self.descs.append(d)
         if PROFILE is not None:
-            self.meta.append((PROFILE.pairs(nbr, n_out), cin, cout, K <= 32 and cin % 32 == 0 and cout % 32 == 0,
-                              "os" if d.os_pairs else "ws" if prod is not None else "tile"))
-        self.keep += [x, nbr, wp, scale, shift, residual, out, plist, prod, w_bf3, os_pairs]
+            self.meta.append((PROFILE.pairs(nbr, d.n_out), cin, cout, K <= 32 and cin % 32 == 0 and cout % 32 == 0,
+                              _route_label(route)))
+        self.keep += keep
         return out
 
     def launch(self):

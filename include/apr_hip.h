@@ -316,21 +316,38 @@ typedef struct apr_spconv_desc {
   const float* w_packed; const float* scale; const float* shift;
   const float* residual; int64_t ldr;
   float* out; int64_t ldo;
+  /* What the caller has for this layer; which of it a launch uses is apr_spconv_route's decision (below). */
   int32_t* counters;      /* pair-list counters and ... */
-  void* plist;            /* ... body; non-NULL: run this launch through apr_spconv_ws_fwd with ... */
-  float* prod_scratch;    /* ... this product buffer (n_out*K rows); */
-  int64_t plist_bytes;    /* > 0: apr_pairlist_build(nbr -> plist) first (first use of the map in the batch) */
-  const void* w_bf3;      /* non-NULL (with plist): apr_spconv_ws_fwd_bf3 with these split weights */
-  void* os_pairs;         /* non-NULL (with w_bf3): run this launch through apr_spconv_os_fwd over these tile lists, */
+  void* plist;            /* ... body (apr_pairlist_build; with ws3: apr_pairlist3_build), with ... */
+  float* prod_scratch;    /* ... the product buffer of the weight-stationary families (n_out*K rows; ws3: 9 * n_out) */
+  int64_t plist_bytes;    /* > 0: the routed family builds plist from nbr first (first use of the map in the batch) */
+  const void* w_bf3;      /* the bf16-split weights (apr_spconv_pack_weights_bf3) */
+  void* os_pairs;         /* the output-stationary tile lists of nbr, */
   int64_t os_rows;        /* ... of os_rows rows per tile; */
   int64_t os_build_bytes; /* > 0: apr_spconv_os_pairs_build(nbr -> os_pairs, n_in = os_n_in) first */
   int64_t os_n_in;
   int32_t l2norm;         /* != 0: out[j, :] /= |out[j, :]|_2 behind the epilogue (the encoder's normalize_feature,
-                           * FCGF_APR/model/resunet.py:139-142): in the tile kernel's epilogue when it runs the layer
-                           * with cout 32 or 64 (same bits as apr_l2_normalize), else as a second launch */
-  int32_t ws3;            /* != 0 (with plist and w_bf3): plist is a TRIPLE pair list (apr_pairlist3_build / _bytes), the launch
-                           * runs through apr_spconv_ws3_fwd_bf3 and prod_scratch holds 9 * n_out rows */
+                           * FCGF_APR/model/resunet.py:139-142): in the tile / dense-rows kernel's epilogue where that
+                           * kernel holds the whole row (same bits as apr_l2_normalize), else as a second launch */
+  int32_t ws3;            /* != 0: plist is a TRIPLE pair list */
 } apr_spconv_desc;
+/* The kernel family a descriptor's launch runs through -- the ONLY place that decides it ("How a conv layer is
+ * routed"; apr_spconv_fwd_batch switches on it).  Host only: no HIP call, no device needed; reads the shape fields, the
+ * leading dimensions, pointer alignment and which pointers are non-NULL, never w_packed -- a caller asks first and builds
+ * the tile pack only for APR_ROUTE_TILE / APR_ROUTE_WS.  >= 0: a route id; < 0: APR_EINVAL, apr_last_error() says why (ws3
+ * set on a weight-stationary shape that the triple lists do not cover, or without w_bf3). */
+enum {
+  APR_ROUTE_TILE = 0,   /* apr_spconv_fwd (with its own choice among the pairs / mfma / small-cin / generic / dense kernels) */
+  APR_ROUTE_WS,         /* apr_spconv_ws_fwd: fp32 weight-stationary, reads w_packed */
+  APR_ROUTE_WS_BF3,     /* apr_spconv_ws_fwd_bf3 on the split weights alone */
+  APR_ROUTE_WS3,        /* apr_spconv_ws3_fwd_bf3 */
+  APR_ROUTE_OS,         /* apr_spconv_os_fwd */
+  APR_ROUTE_DENSE_ROWS, /* apr_dense_rows_bf3 */
+  APR_ROUTE_DENSE_GEMM  /* apr_dense_gemm_bf3 */
+};
+int32_t apr_spconv_route(const apr_spconv_desc* d);
+/* 1 if the weight-stationary families take the shape: K <= 27, cin % 64 == 0, cin <= 512, cout % 64 == 0. */
+int32_t apr_spconv_ws_supported(int32_t K, int32_t cin, int32_t cout);
 int apr_spconv_fwd_batch(const apr_spconv_desc* descs_host, int32_t n, void* stream);
 /* Same, with one HIP event pair per launch recorded on `stream` (around the conv kernels only, not a pair-list
  * build); synchronises and returns each layer's elapsed milliseconds in layer_ms[n].  Measurement aid
