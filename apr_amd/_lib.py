@@ -135,6 +135,7 @@ PROTOTYPES = {
     "apr_spconv_wgrad_same_level": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "apr_spconv_route": (_i32, [_p]),
     "apr_spconv_ws_supported": (_i32, [_i32, _i32, _i32]),
+    "apr_spconv_bigk_supported": (_i32, [_i32, _i32, _i32]),
     "apr_spconv_fwd_batch": (C.c_int, [_p, _i32, _p]),
     "apr_spconv_fwd_batch_timed": (C.c_int, [_p, _i32, _p, _p]),
     "apr_bn_stats": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _sz, _p]),

@@ -74,6 +74,11 @@ int apr_internal_dense_gemm(const float* in, int64_t ldi, int64_t M, int32_t cin
                             const float* scale, const float* shift, const float* residual, int64_t ldr, int32_t relu,
                             float* out, int64_t ldo, hipStream_t st);
 
+// spconv_bigk.hip: the tile family's kernel for 32 < K <= 125 (apr_spconv_bigk_supported shapes); _aligned = the 16-byte
+// rows and vectors it loads and stores by
+bool apr_internal_spconv_bigk_aligned(const apr_spconv_desc& d);
+int apr_internal_spconv_bigk(const apr_spconv_desc& d, hipStream_t st);
+
 // norm.hip: y = act((x - mean) * rstd (+ residual)) per row segment, mean / rstd rebuilt from per-block column sums
 // partial[blk][2][c] (fp64; segment s owns blocks blk0[s] .. blk0[s + 1]) that another kernel left behind
 int apr_internal_norm_apply_partials(const float* x, int64_t ldx, int32_t c, const int64_t* seg_row0, const int* seg_blk0,

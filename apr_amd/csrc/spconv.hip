@@ -628,6 +628,11 @@ static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, b
   }
   APR_CHECK_ARG(!use_mfma(K, cin, cout),
                 "apr_spconv_fwd: MFMA-shaped layer needs 16-B aligned input rows (ldi %% 4 == 0)");
+  // 32 < K <= 125 with real channel counts (the symmetric recipe's 5^3 generator conv1 and its input gradient): the
+  // pair-compacted MFMA kernel of spconv_bigk.hip on the same plain [K, cin, cout] buffer; APR_SPCONV_BIGK=0: generic
+  static const int s_bigk = env_int("APR_SPCONV_BIGK", 1);
+  if (s_bigk && apr_spconv_bigk_supported(K, cin, cout) && apr_internal_spconv_bigk_aligned(d))
+    return apr_internal_spconv_bigk(d, st);
   if (d.nbr && (cin == 1 || cin == 3) && cout % 32 == 0 && (size_t)64 * K * 4 <= 64 * 1024 &&
       (((uintptr_t)d.w_packed) & 15) == 0) {
     const unsigned grid = (unsigned)cdiv64(n_out, 64);

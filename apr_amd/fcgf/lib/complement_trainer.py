@@ -1,11 +1,14 @@
 """One training iteration of APR's FCGF trainer on the HIP kernels.
 
-Mirrors the loop body of `GenerativePairTrainer._train_epoch`, /root/reference/FCGF_APR/lib/complement_trainer.py:350-512
-(the non-symmetric branch the shipped script trains, scripts/train_apr_kitti.sh): both frames through the encoder in
-train mode, the hardest-contrastive loss (:398-409), per cloud of the batch the NPR branch -- generator on the cloud's
-features x voxel size, regulariser (:432-440), generated points = offsets + voxel corner (:441-442), Chamfer distance to
-the APG cloud, `(chamfer + reg * strength) * loss_ratio` (:446-448) -- one backward, one optimizer step.  The epoch loop,
-data loader, logging and checkpoints around it are the reference's own host code and stay out of scope.
+Mirrors the loop body of `GenerativePairTrainer._train_epoch`, /root/reference/FCGF_APR/lib/complement_trainer.py:350-512:
+both frames through the encoder in train mode, the hardest-contrastive loss (:398-409), per cloud of the batch the NPR
+branch -- generator output x voxel size, regulariser (:432-440), generated points = offsets + voxel corner (:441-442),
+Chamfer distance to the APG cloud, `(chamfer + reg * strength) * loss_ratio` (:446-448) -- one backward, one optimizer
+step.  Both shipped recipes: `symmetric=False` (scripts/train_apr_kitti.sh) calls an MLP generator per cloud on the
+cloud's feature rows; `symmetric=True` (scripts/train_apr_nuscenes.sh, whose generator is a second ResUNetFatBN, 128
+channels in, point_generation_ratio * 3 out, lib/complement_trainer.py:52-60) calls a sparse network once per frame on the
+encoder's output tensor (:413-419, :427-428, :459-460).  The epoch loop, data loader, logging and checkpoints around it
+are the reference's own host code and stay out of scope.
 
 Every stage can be bracketed by HIP events on the launch stream (`timed=True`) for the bench's forward / loss / backward
 / optimizer split.
@@ -22,8 +25,11 @@ from .trainer import HardestContrastiveLoss
 class GenerativePairTrainStep:
     def __init__(self, encoder_model, generator_model, optimizer, voxel_size=0.3, point_generation_ratio=6,
                  regularization_strength=0.1, regularization_type='L2', alpha=0.1, loss_ratio=1e-5, neg_weight=1,
-                 num_pos_per_batch=1024, num_hn_samples_per_batch=256, batch_size=1, pos_thresh=0.1, neg_thresh=1.4):
-        # defaults: FCGF_APR/config.py:30-36,77-79,86
+                 num_pos_per_batch=1024, num_hn_samples_per_batch=256, batch_size=1, pos_thresh=0.1, neg_thresh=1.4,
+                 symmetric=False):
+        # defaults: FCGF_APR/config.py:30-36,77-79,86.  `symmetric` (config.py's --symmetric): generator_model is a sparse
+        # network (any apr_amd.fcgf.model.load_model name) applied to the encoder's output SparseTensor
+        self.symmetric = bool(symmetric)
         self.encoder_model, self.generator_model, self.optimizer = encoder_model, generator_model, optimizer
         self.voxel_size = voxel_size
         self.point_generation_ratio = point_generation_ratio
@@ -81,6 +87,55 @@ class GenerativePairTrainStep:
             loss = loss + (cham[i] + reg * self.regularization_strength) * self.loss_ratio
         return loss
 
+    def _recon_symmetric(self, encs, Cs, clouds, rows):
+        """The symmetric NPR branch (:413-419, :427-428, :459-460): the generator is a sparse network called ONCE PER FRAME
+        on the encoder's output tensor -- not detached, so its first convolution's input gradient flows back into the
+        encoder -- and a cloud's rows of its output are the cloud's generated offsets.  With `stack_frames` both calls ride
+        in one walk over the encoder's stacked tensor (forward_on_frames: frame 0's BatchNorm statistics, then frame 1's).
+        The rows of a cloud come from the collate's `len_batch`, else from `decomposed_coordinates_and_features`; the
+        regulariser, the generated points and the Chamfer term are those of the MLP branch."""
+        gen = self.generator_model
+        if self.stack_frames and hasattr(gen, "forward_on_frames"):
+            gens = gen.forward_on_frames(encs)
+        else:
+            gens = [gen(e) for e in encs]
+        known = rows[0] is not None and all(sum(r) == e.F.shape[0] for r, e in zip(rows, encs))
+        if known and sum(len(r) for r in rows) <= 32:
+            offs = [0]
+            for fr in rows:
+                for r in fr:
+                    offs.append(offs[-1] + int(r))
+            generated = torch.cat([g.F for g in gens], 0) * self.voxel_size
+            ratio = self.point_generation_ratio
+            mod = apg.npr_points(generated, torch.cat([c[:, 1:] for c in Cs], 0), self.voxel_size, ratio)
+            cl = [torch.as_tensor(c).to(generated.device, dtype=torch.float32) for fr in clouds for c in fr]
+            b_offs = [0]
+            for c in cl:
+                b_offs.append(b_offs[-1] + int(c.shape[0]))
+            cham = npr.chamfer_distance_batch(mod, [o * ratio for o in offs], torch.cat(cl, 0), b_offs)
+            loss = 0
+            for i, (a, b) in enumerate(zip(offs[:-1], offs[1:])):
+                reg = apg.npr_regulariser(generated[a:b], self.regularization_type, self.alpha)
+                loss = loss + (cham[i] + reg * self.regularization_strength) * self.loss_ratio
+            return loss
+        loss = 0
+        for k in (0, 1):
+            if known:
+                offs = [0]
+                for r in rows[k]:
+                    offs.append(offs[-1] + int(r))
+                coords = [Cs[k][a:b, 1:] for a, b in zip(offs[:-1], offs[1:])]
+                feats = [gens[k].F[a:b] for a, b in zip(offs[:-1], offs[1:])]
+            else:
+                coords = encs[k].decomposed_coordinates_and_features[0]
+                feats = gens[k].decomposed_coordinates_and_features[1]
+            for i in range(len(coords)):
+                generated = feats[i] * self.voxel_size
+                reg = apg.npr_regulariser(generated, self.regularization_type, self.alpha)
+                mod = apg.npr_points(generated, coords[i], self.voxel_size, self.point_generation_ratio)
+                loss = loss + (apg.chamfer_distance(mod, clouds[k][i]) + reg * self.regularization_strength) * self.loss_ratio
+        return loss
+
     def __call__(self, input_dict, draws=None, timed=False):
         dev = torch.device('cuda', torch.cuda.current_device())
         marks = []
@@ -113,7 +168,9 @@ class GenerativePairTrainStep:
         loss = pos_loss + self.neg_weight * neg_loss
         mark()
         Cs = [input_dict['sinput0_C'].to(dev), input_dict['sinput1_C'].to(dev)]
-        if self.stack_frames and rows[0] is not None and all(sum(r) == e.F.shape[0] for r, e in zip(rows, enc)) \
+        if self.symmetric:
+            loss = loss + self._recon_symmetric(enc, Cs, [input_dict['pcd_nghb0'], input_dict['pcd_nghb1']], rows)
+        elif self.stack_frames and rows[0] is not None and all(sum(r) == e.F.shape[0] for r, e in zip(rows, enc)) \
                 and sum(len(r) for r in rows) <= 32 and all(v >= 2 for r in rows for v in r):
             loss = loss + self._recon_stacked(enc, Cs, [input_dict['pcd_nghb0'], input_dict['pcd_nghb1']], rows)
         else:
@@ -178,24 +235,30 @@ def synthetic_batch(dev, seed=0, k=5):
     return out
 
 
-def build_step(dev, n_out=128, lr=0.1):
+def build_step(dev, n_out=128, lr=0.1, symmetric=False):
+    """The step of scripts/train_apr_kitti.sh, or with `symmetric` of scripts/train_apr_nuscenes.sh (a second ResUNetFatBN
+    as generator, lib/complement_trainer.py:52-60; regularization_strength 0.01)."""
     torch.manual_seed(0)
     from ..model import load_model
     enc = load_model("ResUNetFatBN")(1, n_out, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=5, D=3).to(dev)
-    gen = apg.GenerativeMLP_98(in_channel=n_out, out_points=4, bn_momentum=0.05).to(dev)
+    if symmetric:
+        gen = load_model("ResUNetFatBN")(n_out, 4 * 3, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=5, D=3).to(dev)
+    else:
+        gen = apg.GenerativeMLP_98(in_channel=n_out, out_points=4, bn_momentum=0.05).to(dev)
     opt = torch.optim.SGD([{'params': enc.parameters()}, {'params': gen.parameters()}], lr=lr, momentum=0.8,
                           weight_decay=1e-4)
-    return GenerativePairTrainStep(enc, gen, opt, voxel_size=0.3, point_generation_ratio=4, regularization_strength=0.1,
-                                   loss_ratio=2e-3)
+    return GenerativePairTrainStep(enc, gen, opt, voxel_size=0.3, point_generation_ratio=4,
+                                   regularization_strength=0.01 if symmetric else 0.1, loss_ratio=2e-3, symmetric=symmetric)
 
 
 
-def measure(dev, iters=8, lr=0.1, log=None):
+def measure(dev, iters=8, lr=0.1, log=None, symmetric=False):
     """Stage split (HIP events, one synchronised iteration at a time) and the un-synchronised iteration time of the APR
-    training step on one full-size pair -> dict for the bench line."""
+    training step on one full-size pair -> dict for the bench line.  `symmetric`: the step of build_step(symmetric=True)
+    (scripts/symmetric_bench.py); the workload text of the result describes the default."""
     import time
     batch = synthetic_batch(dev)
-    step = build_step(dev, lr=lr)
+    step = build_step(dev, lr=lr, symmetric=symmetric)
     rows, walls, losses = [], [], []
     for it in range(iters + 2):
         np.random.seed(it)

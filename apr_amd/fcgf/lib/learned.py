@@ -19,7 +19,7 @@ from ..pipeline import PairRegistration
 from ..registration import rte_rre
 from . import apg
 from .complement_trainer import GenerativePairTrainStep
-from .validation import GenerativePairValidStep, ValidEpoch
+from .validation import GenerativePairValidStep, SymmetricPairValidStep, ValidEpoch
 
 VAL_SEED_OFFSET = 50000
 SEED_STRIDE = 100000
@@ -69,10 +69,18 @@ def synthetic_pair(dev, seed, n_beams=64, n_azimuth=1875, k=5, spacing=6.0, voxe
     return out, xyz0, xyz1, T
 
 
-def build_models(dev, model="ResUNetFatBN", n_out=128, generator=None, ratio=4, lr=0.1):
-    """Encoder, generator and optimizer of scripts/train_apr_kitti.sh (as `complement_trainer.build_step`), seeded."""
+def build_models(dev, model="ResUNetFatBN", n_out=128, generator=None, ratio=4, lr=0.1, symmetric=False):
+    """Encoder, generator and optimizer of scripts/train_apr_kitti.sh (as `complement_trainer.build_step`), seeded.
+    `symmetric`: of scripts/train_apr_nuscenes.sh -- `generator` names a sparse network of `load_model` (default: the
+    script's ResUNetFatBN) built as lib/complement_trainer.py:52-60 does, n_out channels in, ratio * 3 out."""
     torch.manual_seed(0)
     enc = load_model(model)(1, n_out, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=5, D=3).to(dev)
+    if symmetric:
+        gen = load_model(generator or "ResUNetFatBN")(n_out, ratio * 3, bn_momentum=0.05, normalize_feature=True,
+                                                      conv1_kernel_size=5, D=3).to(dev)
+        opt = torch.optim.SGD([{'params': enc.parameters()}, {'params': gen.parameters()}], lr=lr, momentum=0.8,
+                              weight_decay=1e-4)
+        return enc, gen, opt
     if generator is None:
         generator = "GenerativeMLP_98" if n_out >= 64 else "GenerativeMLP_54"
     gen = getattr(apg, generator)(in_channel=n_out, out_points=ratio, bn_momentum=0.05).to(dev)
@@ -83,8 +91,10 @@ def build_models(dev, model="ResUNetFatBN", n_out=128, generator=None, ratio=4, 
 
 def train_and_validate(dev, n_train, n_val, iterations, model="ResUNetFatBN", n_out=128, n_beams=64, n_azimuth=1875,
                        seed=0, generator=None, k=5, lr=0.1, num_pos=1024, num_hn=256, ransac_iters=200000,
-                       register=True):
-    """-> dict: `valid_before` / `valid_after` (the reference's seven averages on the held-out pairs), their per-pair
+                       register=True, symmetric=False):
+    """`symmetric`: the recipe of scripts/train_apr_nuscenes.sh (sparse generator on the encoder's output tensor,
+    regularization_strength 0.01) instead of scripts/train_apr_kitti.sh's.
+    -> dict: `valid_before` / `valid_after` (the reference's seven averages on the held-out pairs), their per-pair
     `records_before` / `records_after`, `losses` (one float per iteration), `recall` and the mean RTE / RRE of the
     successes when `register`, wall `seconds` per phase.  Iteration `it` trains on pair `it % n_train` after
     `np.random.seed(it)`; every validation epoch starts from `np.random.seed(0)` (the reference's `reset_seed(0)`)."""
@@ -95,10 +105,13 @@ def train_and_validate(dev, n_train, n_val, iterations, model="ResUNetFatBN", n_
     s_train, s_val = pair_seeds(n_train, n_val, seed)
     train = [synthetic_pair(dev, s, n_beams, n_azimuth, k)[0] for s in s_train]
     held = [synthetic_pair(dev, s, n_beams, n_azimuth, k) for s in s_val]
-    enc, gen, opt = build_models(dev, model, n_out, generator, ratio, lr)
-    tstep = GenerativePairTrainStep(enc, gen, opt, voxel_size=vs, point_generation_ratio=ratio, regularization_strength=0.1,
-                                    loss_ratio=2e-3, num_pos_per_batch=num_pos, num_hn_samples_per_batch=num_hn)
-    vstep = GenerativePairValidStep(enc, gen, voxel_size=vs, point_generation_ratio=ratio, regularization_strength=0.1)
+    enc, gen, opt = build_models(dev, model, n_out, generator, ratio, lr, symmetric=symmetric)
+    reg = 0.01 if symmetric else 0.1
+    tstep = GenerativePairTrainStep(enc, gen, opt, voxel_size=vs, point_generation_ratio=ratio, regularization_strength=reg,
+                                    loss_ratio=2e-3, num_pos_per_batch=num_pos, num_hn_samples_per_batch=num_hn,
+                                    symmetric=symmetric)
+    vcls = SymmetricPairValidStep if symmetric else GenerativePairValidStep
+    vstep = vcls(enc, gen, voxel_size=vs, point_generation_ratio=ratio, regularization_strength=reg)
     epoch = ValidEpoch(vstep, [h[0] for h in held])
     torch.cuda.synchronize()
     t["data"] = clock() - t0

@@ -1,7 +1,7 @@
 """The validation pass of APR's FCGF trainer on the HIP kernels, device-resident.
 
-Mirrors `GenerativePairTrainer._valid_epoch` (FCGF_APR/lib/complement_trainer.py:514-681, the non-symmetric branch): per
-held-out pair both frames through the encoder in eval mode, `find_corr(..., subsample_size=5000)`, `est_quad_linear_robust`,
+Mirrors `GenerativePairTrainer._valid_epoch` (FCGF_APR/lib/complement_trainer.py:514-681; `GenerativePairValidStep`: the
+non-symmetric branch, `SymmetricPairValidStep`: the symmetric one): per held-out pair both frames through the encoder in eval mode, `find_corr(..., subsample_size=5000)`, `est_quad_linear_robust`,
 `corr_dist`, RTE, RRE, hit ratio (:555-572) and the NPR validation terms (:583-653); per epoch the seven averages of
 :673-681, which `best_val_metric` selects checkpoints by.
 
@@ -15,8 +15,9 @@ depend on them).  The validation set is fixed (`reset_seed(0)`, :518), so `Gener
 once per pair and `ValidEpoch` keeps the prepared pairs across epochs; the step itself, given a prepared pair, enqueues
 without a host synchronisation.
 
-Out of scope, as in the training step: the symmetric (`SimpleNet`) generator branch (`symmetric=True` raises), the data
-loader, logging, checkpoints.
+Out of scope, as in the training step: the data loader, logging, checkpoints.  The `SimpleNet*` families of
+model/simpleunet.py are not mirrored (`load_model` refuses them): no shipped script selects them -- the symmetric recipe's
+generator is a ResUNetFatBN (scripts/train_apr_nuscenes.sh).
 """
 import numpy as np
 import torch
@@ -47,7 +48,10 @@ class GenerativePairValidStep:
       * frame 1's generated points are compared with `pcd_nghb0[i]`, not `pcd_nghb1[i]` (:643);
       * with `RepelL1` the regulariser is ASSIGNED per cloud (`raw_reg_loss =`, :603, :635) where `L2` / `RepelL2`
         accumulate, so only the last cloud of frame 1 counts.
-    Both models are put into eval() for the call and left in the mode they were in."""
+    Both models are put into eval() for the call and left in the mode they were in.
+
+    This class is the non-symmetric branch and refuses `symmetric=True`; the symmetric branch (the generator is a sparse
+    network on the encoder's output tensor) is `SymmetricPairValidStep`."""
 
     def __init__(self, encoder_model, generator_model, voxel_size=0.3, point_generation_ratio=6,
                  regularization_strength=0.1, regularization_type='L2', alpha=0.1, hit_ratio_thresh=0.1,
@@ -148,6 +152,38 @@ class GenerativePairValidStep:
             self.encoder_model.train(modes[0])
             self.generator_model.train(modes[1])
         return {"sel0": sel0, "sel1": sel1, "nn": nn}
+
+
+class SymmetricPairValidStep(GenerativePairValidStep):
+    """The symmetric branch of `_valid_epoch` (:575-581, :590-591, :622-623; scripts/train_apr_nuscenes.sh): the generator
+    is a sparse network (the script's: ResUNetFatBN, 128 channels in, point_generation_ratio * 3 out) called once per frame
+    on the encoder's output tensor, and a cloud's rows of its output are the cloud's generated offsets.  Everything else,
+    both `strict_reference` behaviours included, is the base class."""
+
+    def __init__(self, encoder_model, generator_model, **kw):
+        kw.pop("symmetric", None)
+        super().__init__(encoder_model, generator_model, **kw)
+        self.symmetric = True
+
+    def _npr_terms(self, enc, pair):
+        ratio, vs = self.point_generation_ratio, self.voxel_size
+        gens = [self.generator_model(e) for e in enc]            # :576-577: frame 0, then frame 1
+        reg, cham, n_clouds = 0, 0, 1
+        for k in (0, 1):
+            rows, G, C = pair.rows[k], gens[k].F, pair.coords[k]
+            n_clouds, r0 = len(rows), 0
+            for i, r in enumerate(rows):
+                generated = G[r0:r0 + r] * vs
+                term = apg.npr_regulariser(generated, self.regularization_type, self.alpha)
+                if self.regularization_type == 'RepelL1' and self.strict_reference:
+                    reg = term
+                else:
+                    reg = reg + term
+                points = apg.npr_points(generated, C[r0:r0 + r, 1:], vs, ratio)
+                target = pair.nghb[0 if self.strict_reference else k][i]
+                cham = cham + apg.chamfer_distance(points, target)
+                r0 += r
+        return cham / (2 * n_clouds), reg / (2 * n_clouds)
 
 
 def reduce_records(rec, regularization_strength):

@@ -348,11 +348,32 @@ class ResUNet2(ME.MinkowskiNetwork):
         x = ME.SparseTensor(torch.cat([t.F for t in tensors], 0), coordinates=torch.cat(coords, 0))
         out = self.forward_train(x, frame_rows=rows)
         res, r0 = [], 0
-        for t, n in zip(tensors, rows):
+        for i, (t, n) in enumerate(zip(tensors, rows)):
             res.append(ME.SparseTensor(out.F[r0:r0 + n], coordinate_map_key=t.coordinate_map_key,
                                        coordinate_manager=t.coordinate_manager))
+            res[-1]._stacked = (out, rows, i)      # the walk's own tensor, for a second network on it (forward_on_frames)
             r0 += n
         return res
+
+    def forward_on_frames(self, tensors):
+        """This network on the outputs of ANOTHER network's forward calls, one call per tensor in order (the symmetric
+        recipe's generator on the two encoded frames, FCGF_APR/lib/complement_trainer.py:413-415).  Where the tensors are the
+        results of one `forward_frames` walk, the calls ride in one walk over that walk's stacked tensor and its coordinate
+        manager -- the voxel pyramid, the kernel maps and the pair lists the first network built are reused, only maps it
+        did not need are new -- with per-call BatchNorm statistics in call order.  Otherwise it simply loops."""
+        tensors = list(tensors)
+        st = [getattr(t, "_stacked", None) for t in tensors]
+        if (len(tensors) >= 2 and all(s is not None and s[0] is st[0][0] and s[2] == i for i, s in enumerate(st))
+                and len(st[0][1]) == len(tensors) and self._can_train_fused(st[0][0])):
+            x, rows = st[0][0], st[0][1]
+            out = self.forward_train(x, frame_rows=rows)
+            res, r0 = [], 0
+            for t, n in zip(tensors, rows):
+                res.append(ME.SparseTensor(out.F[r0:r0 + n], coordinate_map_key=t.coordinate_map_key,
+                                           coordinate_manager=t.coordinate_manager))
+                r0 += n
+            return res
+        return [self(t) for t in tensors]
 
     def forward_train(self, x, frame_rows=None):
         """train() + autograd: the same network as `forward_modular`, walked as 23 fused autograd nodes

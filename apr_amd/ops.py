@@ -661,6 +661,11 @@ def ws_supported(K, cin, cout):
     return bool(_lib_().apr_spconv_ws_supported(int(K), int(cin), int(cout)))
 
 
+def bigk_supported(K, cin, cout):
+    """The tile family runs the shape on its 32 < K <= 125 MFMA kernel (apr_spconv_bigk_supported)."""
+    return bool(_lib_().apr_spconv_bigk_supported(int(K), int(cin), int(cout)))
+
+
 _WS_ROUTES = (_lib.ROUTE_WS, _lib.ROUTE_WS_BF3, _lib.ROUTE_WS3)
 _PACK_ROUTES = (_lib.ROUTE_TILE, _lib.ROUTE_WS)      # the families whose kernels read the tile pack
 

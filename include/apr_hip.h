@@ -348,6 +348,11 @@ enum {
 int32_t apr_spconv_route(const apr_spconv_desc* d);
 /* 1 if the weight-stationary families take the shape: K <= 27, cin % 64 == 0, cin <= 512, cout % 64 == 0. */
 int32_t apr_spconv_ws_supported(int32_t K, int32_t cin, int32_t cout);
+/* 1 if, inside APR_ROUTE_TILE, apr_spconv_fwd runs the shape on the big-kernel MFMA kernel (spconv_bigk.hip) instead of the
+ * generic one: 32 < K <= 125, cin % 32 == 0, cout % 32 == 0 (a 5^3 kernel over real channels: the symmetric recipe's
+ * generator conv1, FCGF_APR/lib/complement_trainer.py:52-60, and its input gradient).  Reads the plain [K, cin, cout]
+ * buffer that apr_spconv_pack_weights leaves for K > 32. */
+int32_t apr_spconv_bigk_supported(int32_t K, int32_t cin, int32_t cout);
 int apr_spconv_fwd_batch(const apr_spconv_desc* descs_host, int32_t n, void* stream);
 /* Same, with one HIP event pair per launch recorded on `stream` (around the conv kernels only, not a pair-list
  * build); synchronises and returns each layer's elapsed milliseconds in layer_ms[n].  Measurement aid

@@ -2,6 +2,10 @@
 prints one JSON line.
 
     python scripts/trained_synthetic.py [--train 8] [--val 8] [--iterations 300] [--k 1] [--model ResUNetFatBN] [--n-out 128]
+                                        [--symmetric]
+
+--symmetric: the recipe of FCGF_APR/scripts/train_apr_nuscenes.sh (a second ResUNetFatBN as generator on the encoder's
+output tensor, point_generation_ratio 4, regularization_strength 0.01, L2, loss_ratio 2e-3, num_complement_one_side 3).
 
 The defaults are what fits about two minutes on one MI355X: most of it is the host ray-casting the scans (two key frames
 and 4k complement scans per pair), not the GPU.
@@ -23,17 +27,22 @@ def main():
     ap.add_argument("--train", type=int, default=8)
     ap.add_argument("--val", type=int, default=8)
     ap.add_argument("--iterations", type=int, default=300)
-    ap.add_argument("--k", type=int, default=1, help="complement scans on each side of a key frame (the trainer uses 5)")
+    ap.add_argument("--k", type=int, default=None,
+                    help="complement scans on each side of a key frame (default 1; 3 with --symmetric; the KITTI trainer uses 5)")
     ap.add_argument("--model", default="ResUNetFatBN")
     ap.add_argument("--n-out", type=int, default=128)
     ap.add_argument("--beams", type=int, default=64)
     ap.add_argument("--azimuth", type=int, default=1875)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ransac-iters", type=int, default=200000)
+    ap.add_argument("--symmetric", action="store_true", help="the nuScenes recipe: sparse generator, 3 complement scans a side")
     a = ap.parse_args()
+    if a.k is None:
+        a.k = 3 if a.symmetric else 1
     r = train_and_validate(torch.device("cuda:0"), a.train, a.val, a.iterations, model=a.model, n_out=a.n_out,
-                           n_beams=a.beams, n_azimuth=a.azimuth, seed=a.seed, k=a.k, ransac_iters=a.ransac_iters)
-    line = {"pairs_train": a.train, "pairs_val": a.val, "iterations": a.iterations, "model": a.model, "n_out": a.n_out,
+                           n_beams=a.beams, n_azimuth=a.azimuth, seed=a.seed, k=a.k, ransac_iters=a.ransac_iters,
+                           symmetric=a.symmetric)
+    line = {"symmetric": a.symmetric, "pairs_train": a.train, "pairs_val": a.val, "iterations": a.iterations, "model": a.model, "n_out": a.n_out,
             "rays": [a.beams, a.azimuth], "complement_scans_per_frame": 2 * a.k, "voxels_val_mean": sum(r["voxels"]) / len(r["voxels"]),
             "valid_before": r["valid_before"], "valid_after": r["valid_after"],
             "loss_first_last": [r["losses"][0], r["losses"][-1]] if r["losses"] else None,
