@@ -189,6 +189,8 @@ PROTOTYPES = {
     "apr_irls_scratch_bytes": (_sz, [_i64]),
     "apr_valid_pair": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _f32, _p, _i64, _i64, _p, _sz, _p]),
     "apr_valid_pair_scratch_bytes": (_sz, [_i64]),
+    "apr_predator_valid_record": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p]),
+    "apr_predator_test_pair": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _f64, _f64, _f64, _f64, _p, _i64, _i64, _p]),
     "apr_contrastive_reduce": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _f32, _f32, _p, _p]),
     "apr_pair_rows_from_nn": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
     "apr_pair_dist": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _f32, _p, _p, _p, _p]),

@@ -15,6 +15,7 @@
 // second launch or a device-scope fence.  The pair-list RANSAC that consumes the list lives in ransac.hip, next to the
 // device functions it shares with the other RANSAC entries.
 #include "common.h"
+#include "inlier_dist.h"
 
 namespace {
 
@@ -64,21 +65,7 @@ __global__ __launch_bounds__(kListThreads) void k_mutual_select(const int* __res
   if (threadIdx.x == 0) *count = min(s_carry, cap);
 }
 
-// benchmark_utils.py:246: (rot @ src.T + trans).T in float32, the products added left to right, every operation rounded
-__device__ inline void transform_f32(const float* __restrict__ rot9, const float* __restrict__ trans3, const float* __restrict__ p,
-                                     float q[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float s = __fadd_rn(__fadd_rn(__fmul_rn(rot9[3 * a], p[0]), __fmul_rn(rot9[3 * a + 1], p[1])),
-                              __fmul_rn(rot9[3 * a + 2], p[2]));
-    q[a] = __fadd_rn(s, trans3[a]);
-  }
-}
-
-__device__ inline float dist_f32(const float q[3], const float* __restrict__ t) {
-  const float dx = __fsub_rn(q[0], t[0]), dy = __fsub_rn(q[1], t[1]), dz = __fsub_rn(q[2], t[2]);
-  return __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-}
+// transform_f32 / dist_f32 (benchmark_utils.py:246, :252 in float32): inlier_dist.h
 
 // block-wide integer sum (every thread calls it); the result is valid in thread 0
 __device__ inline int block_sum(int v, int* s_wave) {

@@ -28,16 +28,9 @@
 
 #include "common.h"
 #include "irls.h"
+#include "ransac_raw.h"      // struct Hyp, kRawBytes, raw_decode20
 
 namespace {
-
-struct Hyp {
-  double T[12];  // row-major [R | t], 3x4
-  long long it;
-  int inliers;
-  int pad;
-  double err2;
-};
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -1194,7 +1187,7 @@ static int band_words(int64_t n0) { return (int)((rec2_rows(n0) / kMini + 31) / 
 
 // raw result = the best hypothesis with total_valid behind it: what apr_ransac_decode reads, and the head of every batch
 // result slot (stride kSlotBytes)
-constexpr size_t kRawBytes = sizeof(Hyp) + 8, kSlotBytes = sizeof(Hyp) + 64;
+constexpr size_t kSlotBytes = sizeof(Hyp) + 64;
 
 static RansacScratch walk_ransac(AprArena& a, int64_t n0, int64_t max_iter) {
   if (max_iter < 1) max_iter = 1;
@@ -1330,12 +1323,7 @@ static long long decode_result(const void* raw, double* result_host) {
   long long tv;
   memcpy(&hb, raw, sizeof(Hyp));
   memcpy(&tv, (const char*)raw + sizeof(Hyp), 8);
-  for (int k = 0; k < 12; ++k) result_host[k] = hb.T[k];
-  result_host[12] = 0.0; result_host[13] = 0.0; result_host[14] = 0.0; result_host[15] = 1.0;
-  result_host[16] = (double)(hb.inliers < 0 ? 0 : hb.inliers);
-  result_host[17] = hb.inliers > 0 ? sqrt(hb.err2 / (double)hb.inliers) : 0.0;
-  result_host[18] = (double)hb.it;
-  result_host[19] = (double)tv;
+  raw_decode20(hb, tv, result_host);
   return tv;
 }
 

@@ -1845,7 +1845,67 @@ def valid_pair(xyz0, xyz1, nn, T_gt, records, slot, sel0=None, sel1=None, hit_th
                              ptr(scratch), sb, stream()))
 
 
-ICP_RECORD_DOUBLES = 20       # APR_ICP_RECORD_DOUBLES
+PVALID_RECORD_FLOATS = 16     # APR_PREDATOR_VALID_RECORD_FLOATS
+# columns of a Predator validation record (include/apr_hip.h: apr_predator_valid_record); [0, 8) are MetricLoss's keys
+PVALID_STATS = ("circle_loss", "recall", "overlap_loss", "overlap_recall", "overlap_precision", "saliency_loss",
+                "saliency_recall", "saliency_precision")
+PVALID_CHAMFER, PVALID_REG, PVALID_COUNT, PVALID_ANCHORS, PVALID_N_SRC, PVALID_N_TGT, PVALID_NAN = 8, 9, 10, 11, 12, 13, 14
+
+
+def _check_numel(t, n, name):
+    if t.numel() != n:
+        raise _lib.AprHipError(f"predator_valid_record: {name} must hold {n} element(s), got {t.numel()}")
+    return t
+
+
+def predator_valid_record(overlap8, saliency8, circle4, count, chamfer0, chamfer1, reg0, reg1, n_src, n_tgt, records, slot):
+    """The stats of one validated Predator pair into `records[slot]` (float32 [pairs, 16] on the GPU, columns `PVALID_*`):
+    the loss kernels' result vectors, the filtered-correspondence count and the two frames' Chamfer / regulariser values
+    (0-d or 1-element float32 GPU tensors).  One launch; does not synchronise and returns nothing."""
+    f = lambda t, n, name: _check_numel(_dev(t, torch.float32, "predator_valid_record." + name), n, name)
+    overlap8, saliency8, circle4 = f(overlap8, 8, "overlap8"), f(saliency8, 8, "saliency8"), f(circle4, 4, "circle4")
+    terms = [f(t, 1, name) for t, name in ((chamfer0, "chamfer0"), (chamfer1, "chamfer1"), (reg0, "reg0"), (reg1, "reg1"))]
+    count = _check_numel(_dev(count, torch.int32, "predator_valid_record.count"), 1, "count")
+    _lib.require_gpu_tensor(records, torch.float32, "predator_valid_record.records")
+    if records.dim() != 2 or records.shape[1] != PVALID_RECORD_FLOATS or not records.is_contiguous():
+        raise _lib.AprHipError(f"predator_valid_record: records must be a contiguous [pairs, {PVALID_RECORD_FLOATS}]")
+    check(_lib_().apr_predator_valid_record(ptr(overlap8), ptr(saliency8), ptr(circle4), ptr(count), ptr(terms[0]),
+                                            ptr(terms[1]), ptr(terms[2]), ptr(terms[3]), int(n_src), int(n_tgt),
+                                            ptr(records), records.shape[0], int(slot), stream()))
+
+
+PTEST_RECORD_FLOATS = 32      # APR_PREDATOR_TEST_RECORD_FLOATS
+# columns of a Predator test record (include/apr_hip.h: apr_predator_test_pair); [8, 24) is the row-major 4x4 estimate
+PTEST_RRE, PTEST_RTE, PTEST_SUCCESS, PTEST_DIST, PTEST_INLIER_GT, PTEST_INLIER_EST, PTEST_NS, PTEST_NT, PTEST_T = range(9)
+PTEST_INLIERS, PTEST_RMSE, PTEST_N_VALID, PTEST_BEST_ITERATION, PTEST_BAD_CORR = 24, 25, 26, 27, 28
+
+
+def predator_test_pair(s_p, t_p, corr, rot, trans, raw, records, slot, distance_threshold=0.3,
+                       inlier_distance_threshold=0.1, rot_threshold=5, trans_threshold=2):
+    """The tester's per-pair figures (lib/tester.py:104-124) from the raw RANSAC result `raw` where
+    `ransac_pose_geometric_async` left it on the GPU, into `records[slot]` (float64 [pairs, 32] on the GPU, columns
+    `PTEST_*`).  One launch; does not synchronise and returns nothing -- read `records` back when the epoch is over."""
+    s_p = _f32(s_p, "predator_test_pair.s_p").contiguous()
+    t_p = _f32(t_p, "predator_test_pair.t_p").contiguous()
+    rot, trans = _dev(rot, torch.float32, "predator_test_pair.rot"), _dev(trans, torch.float32, "predator_test_pair.trans")
+    corr = _dev(corr, torch.int64, "predator_test_pair.corr")
+    raw = _dev(raw, torch.uint8, "predator_test_pair.raw")
+    if s_p.dim() != 2 or s_p.shape[1] != 3 or t_p.dim() != 2 or t_p.shape[1] != 3:
+        raise _lib.AprHipError("predator_test_pair: the clouds must be [n, 3]")
+    if rot.numel() != 9 or trans.numel() != 3 or corr.dim() != 1 or corr.shape[0] != s_p.shape[0]:
+        raise _lib.AprHipError("predator_test_pair: need rot [3,3], trans [3] and one corr entry per source point")
+    lib = _lib_()
+    if raw.numel() < int(lib.apr_ransac_raw_bytes()):
+        raise _lib.AprHipError("predator_test_pair: raw is shorter than a raw RANSAC result")
+    _lib.require_gpu_tensor(records, torch.float64, "predator_test_pair.records")
+    if records.dim() != 2 or records.shape[1] != PTEST_RECORD_FLOATS or not records.is_contiguous():
+        raise _lib.AprHipError(f"predator_test_pair: records must be a contiguous [pairs, {PTEST_RECORD_FLOATS}]")
+    check(lib.apr_predator_test_pair(ptr(s_p), s_p.shape[0], ptr(t_p), t_p.shape[0], ptr(corr), ptr(rot), ptr(trans), ptr(raw),
+                                     float(distance_threshold), float(inlier_distance_threshold), float(rot_threshold),
+                                     float(trans_threshold), ptr(records), records.shape[0], int(slot), stream()))
+
+
+ICP_RECORD_DOUBLES = 20      # APR_ICP_RECORD_DOUBLES
 # columns of an ICP record (include/apr_hip.h: apr_icp_batch); [0, 16) is the row-major 4x4 transform
 ICP_FITNESS, ICP_RMSE, ICP_N_CORR, ICP_ITERATIONS = 16, 17, 18, 19
 

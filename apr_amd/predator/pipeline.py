@@ -123,7 +123,6 @@ class PredatorRegistration:
         (1 + 4 per batch), the neighbour-table widths, the sampling weights, the RANSAC results -- yields an
         ops.PendingFetch instead; all device work goes to the CURRENT stream.  Returns [(T, info), ...]."""
         from .. import ops
-        from .datasets.dataloader import collate_phases
         seeds = list(range(len(pairs))) if seeds is None else list(seeds)
         dev = pairs[0][0].device
         clouds = [c for pair in pairs for c in pair]
@@ -138,7 +137,29 @@ class PredatorRegistration:
         sub = [pts[e - n:e] for e, n in zip(ends, lens)]
         ones = lambda p: torch.ones((len(p), 1), device=dev)
         items = [(sub[2 * i], sub[2 * i + 1], ones(sub[2 * i]), ones(sub[2 * i + 1])) for i in range(len(pairs))]
-        batch = yield from collate_phases(items, self.config, self.limits)
+        raws, n01 = yield from self._match_phases(items, seeds, None)
+        rfetch = ops.PendingFetch(torch.stack(raws), lambda host: host.copy())
+        yield rfetch
+        out = []
+        for raw, (n0, n1, ns) in zip(rfetch.finish(), n01):
+            T, info = ops.ransac_decode(raw, ns)
+            info.update(n0=n0, n1=n1)
+            out.append((T, info))
+        return out
+
+    def _match_phases(self, items, seeds, draws, after=None):
+        """The tail that `register_batch_phases` and `register_samples_phases` share, from the voxelised clouds on:
+        collate, network, the score-weighted draws (lib/tester.py:80-92), feature NN and the RANSAC enqueue of every pair.
+        `items`: per pair (src, tgt, src_feats, tgt_feats, ...) as the collate takes them; the clouds that are sampled and
+        registered are the items' raw clouds where they have them (index 7, 8: `inputs['src_pcd_raw']`), else the inputs.
+        `draws`: None -- pair i draws from its own `np.random.RandomState(seeds[i])`; a `RandomState` or the `np.random`
+        module -- every pair draws from that one stream, source then target, in pair order.  `after(i, s_p, t_p, corr,
+        raw)` runs right behind pair i's RANSAC enqueue.  -> (raw results on the device, [(n0, n1, ns), ...])."""
+        from .. import ops
+        from .datasets.dataloader import collate_phases
+        f32 = lambda p: p.to(torch.float32).contiguous()
+        clouds = [(f32(it[7]), f32(it[8])) if len(it) > 8 else (it[0], it[1]) for it in items]
+        batch = yield from collate_phases([tuple(it[:4]) for it in items], self.config, self.limits)
         feats, overlap, saliency = self.model(batch)
         wfetch = ops.PendingFetch(overlap * saliency, lambda host: host.copy())
         yield wfetch
@@ -146,12 +167,15 @@ class PredatorRegistration:
         # the score-weighted draws of all pairs (NumPy's legacy choice on each pair's own RandomState: 0.39 ms of host time
         # per pair, most of it inside the library's host function, which releases the GIL) run on a helper thread while the
         # scheduler thread serves the other batches
-        spans = [(int(ends[2 * i] - lens[2 * i]), int(lens[2 * i]), int(lens[2 * i + 1])) for i in range(len(pairs))]
+        spans, a = [], 0
+        for it in items:
+            spans.append((a, len(it[0]), len(it[1])))
+            a += len(it[0]) + len(it[1])
 
         def draw_all():
             out_ = []
             for (a, n0, n1), seed in zip(spans, seeds):
-                rng = np.random.RandomState(seed)
+                rng = np.random.RandomState(seed) if draws is None else draws
                 i0 = BU.draw_by_score(n0, w_all[a:a + n0], self.n_points, rng)
                 i1 = BU.draw_by_score(n1, w_all[a + n0:a + n0 + n1], self.n_points, rng)
                 out_.append((i0, i1))
@@ -164,20 +188,51 @@ class PredatorRegistration:
         for i, seed in enumerate(seeds):
             a, n0, n1 = spans[i]
             b = a + n0 + n1
-            s_p, s_f = BU.take_drawn(sub[2 * i], feats[a:a + n0], drawn[i][0])
-            t_p, t_f = BU.take_drawn(sub[2 * i + 1], feats[a + n0:b], drawn[i][1])
+            s_p, s_f = BU.take_drawn(clouds[i][0], feats[a:a + n0], drawn[i][0])
+            t_p, t_f = BU.take_drawn(clouds[i][1], feats[a + n0:b], drawn[i][1])
             corr = ops.feature_nn(s_f.contiguous(), t_f.contiguous())
             raws.append(ops.ransac_pose_geometric_async(s_p, t_p, corr, self.distance_threshold, 0.9, self.max_iteration,
                                                         self.max_validation, seed))
             n01.append((n0, n1, len(s_p)))
-        rfetch = ops.PendingFetch(torch.stack(raws), lambda host: host.copy())
-        yield rfetch
-        out = []
-        for raw, (n0, n1, ns) in zip(rfetch.finish(), n01):
-            T, info = ops.ransac_decode(raw, ns)
-            info.update(n0=n0, n1=n1)
-            out.append((T, info))
-        return out
+            if after is not None:
+                after(i, s_p, t_p, corr, raws[-1])
+        return raws, n01
+
+    @torch.no_grad()
+    def register_samples_phases(self, items, draws=None, seeds=None, records=None, slot0=0, rot_threshold=5,
+                                trans_threshold=2, inlier_distance_threshold=0.1):
+        """The tail of `register_batch_phases` for clouds the loader already voxelised: `items` are
+        `datasets.kitti.test_sample` / `training_sample` tuples (or any (src, tgt, src_feats, tgt_feats, rot, trans, ...)),
+        no voxeliser call is made.  Behind each pair's RANSAC enqueue, `ops.predator_test_pair` turns the raw result into
+        row `slot0 + i` of `records` (float64 [pairs, 32] on the GPU, columns `ops.PTEST_*`; None: a buffer of len(items)
+        rows): no raw result travels to the host, the caller reads `records` once when its epoch is over.
+        `draws` / `seeds`: see `_match_phases`; `seeds` are the RANSAC seeds too (default: the pair index).
+        Returns `records`."""
+        from .. import ops
+        items = list(items)
+        seeds = list(range(len(items))) if seeds is None else list(seeds)
+        if len(seeds) != len(items):
+            raise ValueError(f"register_samples: {len(items)} pairs but {len(seeds)} seeds")
+        dev = items[0][0].device
+        if records is None:
+            records = torch.zeros((slot0 + len(items), ops.PTEST_RECORD_FLOATS), dtype=torch.float64, device=dev)
+        gt = [(it[4].to(dev, torch.float32).reshape(3, 3).contiguous(), it[5].to(dev, torch.float32).reshape(3).contiguous())
+              for it in items]
+
+        def after(i, s_p, t_p, corr, raw):
+            ops.predator_test_pair(s_p, t_p, corr, gt[i][0], gt[i][1], raw, records, slot0 + i,
+                                   distance_threshold=self.distance_threshold,
+                                   inlier_distance_threshold=inlier_distance_threshold, rot_threshold=rot_threshold,
+                                   trans_threshold=trans_threshold)
+
+        yield from self._match_phases(items, seeds, draws, after)
+        return records
+
+    @torch.no_grad()
+    def register_samples(self, items, draws=None, seeds=None, **kw):
+        """`register_samples_phases`, waited for -> the records on the host (float64 [pairs, 32]), fetched once."""
+        from .. import ops
+        return ops.drive(self.register_samples_phases(items, draws, seeds, **kw)).cpu().numpy()
 
     @torch.no_grad()
     def __call__(self, xyz0, xyz1, seed=0):

@@ -658,6 +658,46 @@ int apr_valid_pair(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1,
                    size_t scratch_bytes, void* stream);
 size_t apr_valid_pair_scratch_bytes(int64_t m0);
 
+/* The record of one validated Predator pair, replaces the stat picking, the two additions and the five float()
+ *   synchronisations at the end of Trainer.inference_one_batch(inputs, 'val') (Predator_APR/lib/trainer.py:253-278).
+ * One small launch, nothing synchronises.  Device pointers: overlap8 / saliency8 f32[8]: the apr_weighted_bce_forward
+ *   results of the overlap and the saliency scores (loss, w_negative, precision, recall, ...); circle4 f32[4]: the
+ *   apr_circle_forward result (circle_loss, recall, anchors used, ...); count i32[1]: the filtered correspondences
+ *   (apr_circle_select); chamfer0/1, reg0/1 f32[1]: the two frames' Chamfer and regulariser values.  n_src, n_tgt: rows
+ *   of the two clouds (host values, < 2^24).
+ * Writes record `slot` of records f32[n_slots, APR_PREDATOR_VALID_RECORD_FLOATS]:
+ *   [0..7] circle_loss, recall, overlap_loss, overlap_recall, overlap_precision, saliency_loss, saliency_recall,
+ *          saliency_precision (lib/loss.py:99-178)
+ *   [8] chamfer_loss = chamfer0 + chamfer1        [9] regularization_loss = reg0 + reg1 (float32 adds, :253-264)
+ *   [10] filtered count   [11] anchors used   [12] n_src   [13] n_tgt   [14] how many of chamfer0/1 are NaN   [15] 0 */
+#define APR_PREDATOR_VALID_RECORD_FLOATS 16
+int apr_predator_valid_record(const float* overlap8, const float* saliency8, const float* circle4,
+                              const int32_t* count, const float* chamfer0, const float* chamfer1, const float* reg0,
+                              const float* reg1, int64_t n_src, int64_t n_tgt, float* records, int64_t n_slots,
+                              int64_t slot, void* stream);
+
+/* The record of one tested Predator pair: what KITTITester.test / NUSCENESTester.test compute on the host after their
+ *   per-pair loop (Predator_APR/lib/tester.py:104-124, the same statements at the end of NUSCENESTester.test, :158-268;
+ *   get_angle_deviation lib/benchmark_utils.py:170-185), taken
+ *   from the RAW RANSAC result on the device (raw_dev: what apr_ransac_pose_geometric_async left, apr_ransac_raw_bytes()
+ *   bytes, 8-byte aligned).  One launch of one 1024-thread workgroup, nothing synchronises, sums in a fixed order.
+ *   s_p f32[ns,3], t_p f32[nt,3]: the sampled clouds; corr i64[ns]: feature nearest neighbour of source row i;
+ *   rot_gt f32[9], trans_gt f32[3]: the pair's ground truth; distance_threshold: the RANSAC distance; 0 < ns < 2^24.
+ * Writes record `slot` of records f64[n_slots, APR_PREDATOR_TEST_RECORD_FLOATS]:
+ *   [0] RRE in degrees = arccos(clip((trace(R_est R_gt^T) - 1) / 2, -1, 1)) / pi * 180 in double
+ *   [1] RTE = |t_est - t_gt|    [2] 1.0 if RRE < rot_threshold && RTE < trans_threshold (both strict), else 0.0
+ *   [3] |t_gt|
+ *   [4] share of rows with |rot_gt s_p[i] + trans_gt - t_p[corr[i]]| < inlier_distance_threshold, in the float32
+ *       arithmetic of apr_inlier_ratio's 'wo' leg       [5] the same under the estimate at distance_threshold
+ *   [6] ns   [7] nt   [8..23] the estimate, row-major 4x4, as apr_ransac_decode gives it
+ *   [24] inliers   [25] rmse   [26] n_valid (total_valid)   [27] best iteration
+ *   [28] corr entries outside [0, nt): such a row reads target row 0 and is counted      [29..31] 0 */
+#define APR_PREDATOR_TEST_RECORD_FLOATS 32
+int apr_predator_test_pair(const float* s_p, int64_t ns, const float* t_p, int64_t nt, const int64_t* corr,
+                           const float* rot_gt, const float* trans_gt, const void* raw_dev, double distance_threshold,
+                           double inlier_distance_threshold, double rot_threshold, double trans_threshold,
+                           double* records, int64_t n_slots, int64_t slot, void* stream);
+
 /* Hardest-contrastive mining (forward), replaces the mining + masking + loss arithmetic of
  *   contrastive_hardest_negative_loss (FCGF_APR/lib/trainer.py:400-452, `_hash` util/misc.py:6-18).
  *   pos_f0/pos_f1 f32[p,c]: features of the sampled positive pairs; nn01/nn10 u64[p]: packed
