@@ -1,0 +1,258 @@
+"""Float64 NumPy statement of the kernels of the overlap-attention module (apr_amd/csrc/kpconv.hip from k_edge_features
+on: edge features and their backward, group max, the attention and softmax-matvec kernels, the attention's training
+path, the score head), with per-element error bounds for a float32 evaluation.  numpy only, no torch.
+
+Contract, as the kernels state it
+---------------------------------
+* edge features: f [n, c], knn [n, k] -> e [n * k, 2 c]:  e[(i, j), :c] = f[i],  e[(i, j), c:] = f[knn[i, j]] - f[i].
+* their backward: de [n * k, 2 c] -> d_center[i] = sum_j (de[(i, j), :c] - de[(i, j), c:]),  contrib[(i, j)] = de[(i, j), c:].
+* group max: y [n * k, c] -> out[i] = max_j leaky(y[i k + j] * scale + shift, slope), an absent scale / shift read as 1 / 0,
+  leaky(z) = z for z > 0 and z * slope otherwise.
+* multi-head attention: q [n, dim * H], k, v [m, dim * H] in the INTERLEAVED channel layout d * H + h:
+      out[i, d * H + h] = sum_j softmax_j( sum_d q[i, d, h] k[j, d, h] / sqrt(dim) ) v[j, d, h].
+  The head-major layout h * dim + d is the layout of the INPUTS of apr_mha_headmajor only (headmajor_perm is the
+  permutation apr_amd/predator/models/gcn.py applies to the projections); its output is interleaved.
+* softmax-matvec: a [n, c], b [m, c], w [m], T > 0:  out[i] = sum_j softmax_j(<a_i, b_j> / T) w_j.
+* training path: P [H, n, m] the probabilities above, O = P V with vdim channels per head (dim, or 1 with one head);
+  backward  dV = P^T dO,  dP_j = <dO_i, v_j>,  D = sum_j P_j dP_j,  dS = P o (dP - D),  dQ = dS K / sqrt(dim),
+  dK = dS^T Q / sqrt(dim).
+* score head: finite x -> clamp(sigmoid(x), 0, 1); NaN -> 0, +Inf -> 1, -Inf -> 0, all exactly; rounded to float32,
+  x = -200 is exactly 0 and x = 200 exactly 1.
+
+Error bounds (u = 2^-24; every basic fp32 operation, fused or not, rounds once with relative error <= u; sums in any order)
+----------------------------------------------------------------------------------------------------------------------
+Exact (np.array_equal): e[:, :c], contrib, the score-head specials, and e[:, c:] against the float32 subtraction.
+
+Group max.  z = y * scale + shift is one rounding when contracted (u |z|) and two otherwise (u |y scale| + u |z|):
+b_z = u (2 |y scale| + |z|) covers both.  leaky is Lipschitz with constant L = max(1, |slope|) and continuous at 0, so a
+sign decided differently inside b_z costs no more than L b_z; the product with slope rounds once more.  max_j is
+1-Lipschitz in the sup norm:   |out' - out| <= max_j ( L b_z + u |leaky(z)| ).
+
+d_center.  Every term a - b rounds once, the k additions once each:  (k + 1) u sum_j |a_j - b_j|.
+
+Score head.  e = exp(-x) carries E_exp(x); 1 + e and the division (not necessarily correctly rounded: 2 u) 3 u; with
+y = 1 / (1 + e), dy / y = -(1 - y) de / e:   |y' - y| <= y ((1 - y) E_exp(x) + 3 u) + 2^-126 (a result below the normal
+range may be flushed).
+
+E_exp(t) = (ULP_EXP + 2 |t|) u: the error of expf and also of __expf evaluated as exp2(t * log2 e) on the hardware exp2
+(the product and the constant each add |t| u to the argument).  ULP_EXP = 2: the documents installed with ROCm
+state no accuracy for the device expf (none of them mentions the function), so the value is the agreed default, i.e. one
+unit in the last place (2 u); it is small against the dot-product term at every dimension tested.  A GPU ratio above 1 that
+traces to the exponential alone is to be reported with the float64 exp of the same float32 argument, not absorbed here.
+
+Softmax-weighted sums (apr_mha, apr_mha_headmajor, the three softmax-matvec kernels, the training forward's O).  With
+p_j the exact probabilities and the computed un-normalised weight of key j off by the relative error eps_j,
+    out' - out = sum_j p_j eps_j (v_j - out) / (1 + sum_j p_j eps_j)              (exact identity)
+and every factor common to all keys cancels.  The error of the subtracted maximum is such a factor.
+    eps_j = u (dim * scale * sum_d |q_d k_jd| + 3 |s_j|) + u |t_j| + E_exp(t_j),      t_j = s_j - max_j s_j:
+the dot product in any order (dim roundings at most on any path) times the scale, the scale itself (square root,
+reciprocal or division, product: 3 u |s_j|), the subtraction, the exponential.  A kernel that keeps a running maximum
+writes exp(t_j) as a product exp(s_j - m_1) exp(m_1 - m_2) ... exp(m_r - max): the arguments telescope to t_j, so the
+|t| parts of E_exp add up to those of E_exp(t_j); the ULP_EXP u of every further factor and the rounding of the product
+with it are counted in S below (a factor's error is common to numerator and denominator of the partial sums it
+multiplies, so it acts on out like an error of those keys' weights: at most delta (sum_j p_j |v_j| + |out|)).
+Accumulation:  S u (sum_j p_j |v_j| + |out|) with
+    S = m + (1 + ULP_EXP) (ceil(m / 16) + 3) + 32 + ULP_EXP + 2:
+m roundings for sum_j e_j v_j (one fused step per key, or a product and m - 1 additions) on the numerator and m - 1
+on the denominator; rescale steps: k_mha_mfma rescales once per 16-key tile a wave sees (<= ceil(m / 16)),
+k_softmax_matvec_mfma at most once per key a lane sees (4 ceil(ceil(m / 16) / 8) <= ceil(m / 16) + 3), each a
+product rounding and a factor with its own ULP_EXP u; the merge: at most 32 partial triples, one fused step each, one
+exponential factor; the final division, or reciprocal and product (2).  The scalar kernels (no rescale, an LDS tree)
+stay below the same count.
+Flushed denormal weights: 2^-126 sum_j (|v_j| + |out|).  Second-order terms: the denominator 1 - sum_j p_j eps_j is kept,
+everything is multiplied by 1 + 2^-10.
+
+Training path, to first order in the float64 quantities (absolute bounds: dP_j - D cancels):
+    dlt P_j = P_j (eps_j + sum_j p_j eps_j + (m + 3) u) + 2 * 2^-126     (the sum's m - 1 additions, reciprocal, product, store)
+    O       the bound of the softmax-weighted sums above: the stored P_j is e_j / sum_j e_j, so the identity holds, and the
+            rounding of each stored P_j (reciprocal, product) is inside the slack of S
+    dlt dV  = sum_i dlt P_ij |dO_i| + (n + 1) u sum_i P_ij |dO_i|
+    dlt dP_j = vdim u sum_e |dO_ie| |v_je|
+    dlt D   = sum_j (dlt P_j |dP_j| + P_j dlt dP_j) + (m + 1) u sum_j P_j |dP_j|
+    dlt dS_j = dlt P_j |dP_j - D| + P_j (dlt dP_j + dlt D + 2 u |dP_j - D|) + 2^-126
+    dlt dQ  = scale (sum_j dlt dS_j |k_j| + (m + 4) u sum_j |dS_j| |k_j|),   dlt dK likewise over i with n + 4
+(the scale's square root, reciprocal and product are the 3 of m + 4), all times 1 + 2^-10, plus 2^-126.
+"""
+import numpy as np
+
+from kpconv_oracle import compare_rows      # noqa: F401  (the same comparison, for any rank)
+
+U = 2.0 ** -24
+ULP_EXP = 2.0
+TINY = 2.0 ** -126
+SECOND_ORDER = 1.0 + 2.0 ** -10
+F32 = np.float32
+
+
+def _f64(*arrays):
+    return [np.asarray(a, np.float64) for a in arrays]
+
+
+# ------------------------------------------------------------------------------------------------------ edge kernels
+def edge_features(f, knn):
+    f, = _f64(f)
+    knn = np.asarray(knn, np.int64)
+    n, k = knn.shape
+    ctr = np.repeat(f, k, axis=0)
+    return np.concatenate([ctr, f[knn.reshape(-1)] - ctr], axis=1)
+
+
+def edge_features_f32(f, knn):
+    """the float32 subtraction the second half must equal bit for bit"""
+    f = np.asarray(f, F32)
+    knn = np.asarray(knn, np.int64)
+    ctr = np.repeat(f, knn.shape[1], axis=0)
+    return np.concatenate([ctr, f[knn.reshape(-1)] - ctr], axis=1)
+
+
+def edge_features_backward(de, n, k):
+    """-> d_center [n, c], contrib [n * k, c], bound of d_center"""
+    de, = _f64(de)
+    c = de.shape[1] // 2
+    diff = (de[:, :c] - de[:, c:]).reshape(n, k, c)
+    bound = (k + 1) * U * np.abs(diff).sum(1) * SECOND_ORDER
+    return diff.sum(1), de[:, c:].copy(), bound
+
+
+def leaky(z, slope):
+    return np.where(z > 0, z, z * slope)
+
+
+def group_max(y, n, k, scale, shift, slope):
+    """-> out [n, c], bound [n, c]"""
+    y, = _f64(y)
+    c = y.shape[1]
+    sc = np.ones(c) if scale is None else np.asarray(scale, np.float64)
+    sh = np.zeros(c) if shift is None else np.asarray(shift, np.float64)
+    z = y * sc + sh
+    a = leaky(z, float(slope))
+    b = max(1.0, abs(float(slope))) * U * (2 * np.abs(y * sc) + np.abs(z)) + U * np.abs(a)
+    return a.reshape(n, k, c).max(1), b.reshape(n, k, c).max(1) * SECOND_ORDER
+
+
+# ------------------------------------------------------------------------------------------------------- score head
+def e_exp(t):
+    return (ULP_EXP + 2 * np.abs(t)) * U
+
+
+def score_head(x):
+    """-> y float64 [n] (specials as the contract states them), bound [n]"""
+    x, = _f64(x)
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = 1.0 / (1.0 + np.exp(-x))
+    y = np.clip(y, 0.0, 1.0)
+    y = np.where(np.isnan(x), 0.0, y)
+    fin = np.isfinite(x)
+    xs = np.where(fin, x, 0.0)
+    bound = np.where(fin, (y * ((1 - y) * e_exp(xs) + 3 * U) + TINY) * SECOND_ORDER, 0.0)
+    return y, bound
+
+
+# ------------------------------------------------------------------------------------------------------ softmax sums
+def s_count(m):
+    return m + (1 + ULP_EXP) * (-(-m // 16) + 3) + 32 + ULP_EXP + 2
+
+
+def softmax_core(Q, K, scale):
+    """Q [n, d], K [m, d] -> S, T, P, eps, each [n, m]"""
+    Q, K = _f64(Q, K)
+    d = Q.shape[1]
+    S = (Q @ K.T) * scale
+    T = S - S.max(1, keepdims=True)
+    E = np.exp(T)
+    P = E / E.sum(1, keepdims=True)
+    A = (np.abs(Q) @ np.abs(K).T) * scale
+    eps = U * (d * A + 3 * np.abs(S)) + U * np.abs(T) + e_exp(T)
+    return S, T, P, eps
+
+
+def _weighted_spread(W, V, out):
+    """sum_j W[i, j] |V[j, e] - out[i, e]| -> [n, e], in chunks of queries"""
+    n, m = W.shape
+    res = np.empty_like(out)
+    step = max(1, int(4e6 // max(1, m * V.shape[1])))
+    for i0 in range(0, n, step):
+        sl = slice(i0, i0 + step)
+        res[sl] = np.einsum("ij,ije->ie", W[sl], np.abs(V[None, :, :] - out[sl, None, :]))
+    return res
+
+
+def softmax_sum(Q, K, V, scale):
+    """one head: -> out [n, e], bound [n, e], P [n, m]"""
+    V, = _f64(V)
+    m = len(V)
+    _, _, P, eps = softmax_core(Q, K, scale)
+    out = P @ V
+    pe = (P * eps).sum(1)
+    assert pe.max() < 0.25, "the first-order bound needs sum_j p_j eps_j well below 1"
+    first = _weighted_spread(P * eps, V, out) / (1.0 - pe)[:, None]
+    acc = s_count(m) * U * (P @ np.abs(V) + np.abs(out))
+    den = TINY * (np.abs(V).sum(0)[None, :] + m * np.abs(out))
+    return out, SECOND_ORDER * (first + acc + den), P
+
+
+def heads_of(x, H):
+    """interleaved [r, d * H + h] -> [H, r, d]"""
+    x = np.asarray(x)
+    return x.reshape(len(x), x.shape[1] // H, H).transpose(2, 0, 1)
+
+
+def interleave(xh):
+    """[H, r, d] -> [r, d * H + h]"""
+    H, r, d = xh.shape
+    return np.ascontiguousarray(xh.transpose(1, 2, 0)).reshape(r, d * H)
+
+
+def headmajor_perm(c, H):
+    """new channel h * dim + d <- interleaved channel d * H + h"""
+    return np.arange(c).reshape(c // H, H).T.reshape(-1)
+
+
+def mha(q, k, v, H):
+    """interleaved q [n, c], k [m, c], v [m, cv] -> out [n, cv], bound [n, cv], P [H, n, m]"""
+    qh, kh, vh = heads_of(q, H), heads_of(k, H), heads_of(v, H)
+    scale = 1.0 / np.sqrt(qh.shape[2])
+    res = [softmax_sum(qh[h], kh[h], vh[h], scale) for h in range(H)]
+    return interleave(np.stack([r[0] for r in res])), interleave(np.stack([r[1] for r in res])), np.stack([r[2] for r in res])
+
+
+def softmax_matvec(a, b, w, temperature):
+    """-> out [n], bound [n]"""
+    out, bound, _ = softmax_sum(a, b, np.asarray(w, np.float64).reshape(-1, 1), 1.0 / float(temperature))
+    return out[:, 0], bound[:, 0]
+
+
+# ---------------------------------------------------------------------------------------------------- training path
+def mha_train(q, k, v, dout, H):
+    """-> dict of (value, bound) for P [H, n, m], O [n, cv], dq, dk, dv (interleaved layouts)"""
+    qh, kh, vh, gh = (heads_of(np.asarray(t, np.float64), H) for t in (q, k, v, dout))
+    n, m, dim, vdim = qh.shape[1], kh.shape[1], qh.shape[2], vh.shape[2]
+    scale = 1.0 / np.sqrt(dim)
+    val = {key: [] for key in ("P", "O", "dq", "dk", "dv")}
+    bnd = {key: [] for key in val}
+    for h in range(H):
+        Q, K, V, G = qh[h], kh[h], vh[h], gh[h]
+        _, _, P, eps = softmax_core(Q, K, scale)
+        aV, aG, aQ, aK = np.abs(V), np.abs(G), np.abs(Q), np.abs(K)
+        dP_ = P * (eps + (P * eps).sum(1, keepdims=True) + (m + 3) * U) + 2 * TINY
+        O, dO_, _ = softmax_sum(Q, K, V, scale)      # the stored P is e_j / sum: the identity of the weighted sums holds
+        dV = P.T @ G
+        dV_ = dP_.T @ aG + (n + 1) * U * (P.T @ aG)
+        dPm = G @ V.T
+        ddP_ = vdim * U * (aG @ aV.T)
+        D = (P * dPm).sum(1, keepdims=True)
+        dD_ = (dP_ * np.abs(dPm) + P * ddP_).sum(1, keepdims=True) + (m + 1) * U * (P * np.abs(dPm)).sum(1, keepdims=True)
+        dS = P * (dPm - D)
+        ddS_ = dP_ * np.abs(dPm - D) + P * (ddP_ + dD_ + 2 * U * np.abs(dPm - D)) + TINY
+        dQ = scale * (dS @ K)
+        dQ_ = scale * (ddS_ @ aK + (m + 4) * U * (np.abs(dS) @ aK)) + TINY
+        dK = scale * (dS.T @ Q)
+        dK_ = scale * (ddS_.T @ aQ + (n + 4) * U * (np.abs(dS).T @ aQ)) + TINY
+        for key, x, b in (("P", P, dP_ * SECOND_ORDER), ("O", O, dO_), ("dq", dQ, dQ_ * SECOND_ORDER), ("dk", dK, dK_ * SECOND_ORDER),
+                          ("dv", dV, (dV_ + TINY) * SECOND_ORDER)):
+            val[key].append(x)
+            bnd[key].append(b)
+    out = {"P": (np.stack(val["P"]), np.stack(bnd["P"]))}
+    for key in ("O", "dq", "dk", "dv"):
+        out[key] = (interleave(np.stack(val[key])), interleave(np.stack(bnd[key])))
+    return out
