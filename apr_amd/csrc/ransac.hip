@@ -1481,6 +1481,32 @@ APR_API int apr_ransac_pose(const float* xyz0, int64_t n0, const float* xyz1, in
   return APR_OK;
 }
 
+// apr_ransac_pose without the host synchronisation: ALL max_iter iterations in one round (the fast path above, the per-pair
+// body of apr_match_pose_batch_enqueue below), the raw result copied to `raw_dev`.  Called per pair by the FCGF tester epoch
+// (apr_amd/fcgf/lib/tester.py: FCGFTestEpoch.epoch through ops.ransac_pose_async), whose record kernel
+// (fcgf_test.hip) reads raw_dev on the device.  The result is apr_ransac_pose's whenever total_valid <= 2^20 or
+// max_iter <= 2^20; otherwise the hypothesis list of the single round overflowed, the pose is not final and the caller
+// redoes the pair through apr_ransac_pose (the record's column 28 says so).  Scratch: apr_ransac_scratch_bytes serves.
+APR_API int apr_ransac_pose_async(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int64_t* corr,
+                                  double max_dist, double edge_ratio, int64_t max_iter, uint64_t seed, void* scratch,
+                                  size_t scratch_bytes, void* raw_dev, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  APR_CHECK_ARG(xyz0 && xyz1 && corr && scratch && raw_dev, "apr_ransac_pose_async: NULL argument");
+  APR_CHECK_ARG(n0 > 0 && n0 < (1ll << 31) && n1 > 0, "apr_ransac_pose_async: empty point set");
+  APR_CHECK_ARG(max_iter > 0 && max_iter < (1ll << 31) && max_dist > 0, "apr_ransac_pose_async: bad max_iter / max_dist");
+  AprArena arena(scratch);
+  const RansacScratch r = walk_ransac(arena, n0, max_iter);
+  APR_CHECK_ARG(arena.fits(scratch_bytes), "apr_ransac_pose_async: scratch too small");
+  const int64_t cap = max_iter < kChunk ? max_iter : kChunk;
+  const double thr_lt = sqrt_lt_threshold(max_dist);
+  hipLaunchKernelGGL(k_init_best, dim3(1), dim3(128), 0, st, r.best, r.total_valid, r.maxn2, r.n_valid, counter_words(r));
+  launch_pack(r, xyz0, xyz1, n1, corr, n0, st);
+  launch_hypotheses(r, n0, max_dist, edge_ratio, 0, max_iter, seed, (int)cap, st, true);
+  launch_scoring(r, n0, thr_lt, (int)cap, st);
+  APR_LAUNCH_CHECK();
+  return copy_raw(raw_dev, r.best, r.total_valid, hipMemcpyDeviceToDevice, st);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // B pairs in ONE call: per pair the feature NN (filter + refine, or brute force for other channel counts) and the
 // single-round RANSAC are enqueued back to back on `stream`; the big work buffers are shared (stream order

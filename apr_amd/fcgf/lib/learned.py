@@ -4,6 +4,9 @@ descriptors).
 
     validate (fresh models) -> `iterations` x GenerativePairTrainStep over the training pairs -> validate -> register
 
+`train_and_test` trains with APR's recipe or the FCGF baseline's and then runs the reference's tester epoch
+(`tester.FCGFTestEpoch`: scripts/test_apr.py / scripts/test_fcgf.py) on the held-out pairs.
+
 Pairs come from `synth.make_pair` with disjoint train / held-out seeds, assembled with the recipe of
 `complement_trainer.synthetic_batch` (voxelised key frames, APG clouds from 2k complement scans, GT correspondences
 within 1.5 voxels) plus the validation keys `pcd0`, `pcd1`, `T_gt`.
@@ -19,6 +22,8 @@ from ..pipeline import PairRegistration
 from ..registration import rte_rre
 from . import apg
 from .complement_trainer import GenerativePairTrainStep
+from .pair_trainer import PairTrainStep
+from .tester import FCGFTestEpoch, fmr_table
 from .validation import GenerativePairValidStep, SymmetricPairValidStep, ValidEpoch
 
 VAL_SEED_OFFSET = 50000
@@ -154,3 +159,57 @@ def train_and_validate(dev, n_train, n_val, iterations, model="ResUNetFatBN", n_
     t["total"] = clock() - t0
     out["seconds"] = t
     return out
+
+
+def train_and_test(dev, n_train, n_test, iterations, trainer='apr', symmetric=False, model="ResUNetFatBN", n_out=128,
+                   n_beams=64, n_azimuth=1875, seed=0, generator=None, k=5, lr=0.1, num_pos=1024, num_hn=256,
+                   ransac_iters=4000000, subsample_size=5000, n_points=5000, pairs_per_fetch=64):
+    """Train, then run the reference's tester on held-out synthetic pairs.  `trainer='apr'`: APR's recipe
+    (`GenerativePairTrainStep`; `symmetric` as in `train_and_validate`), tested as scripts/test_apr.py does;
+    `trainer='fcgf'`: the FCGF baseline (`PairTrainStep`, hardest contrastive loss), tested as scripts/test_fcgf.py does
+    (`FCGFTestEpoch(variant=trainer)`).  Iteration `it` trains on pair `it % n_train` after `np.random.seed(it)`; the test
+    epoch starts from `np.random.seed(0)` with the pair index as RANSAC seed.
+    -> dict: `losses` (one float per iteration), `summary` (`tester.test_summary`'s keys with `recall`, plus `n_replayed`),
+    `fmr` (`tester.fmr_table`), `records` (float64 [n_test, 48]), `recall`, `n_replayed`, `train_seeds`, `test_seeds`,
+    `voxels`, wall `seconds` per phase."""
+    if trainer not in ("apr", "fcgf"):
+        raise ValueError(f"train_and_test: trainer {trainer!r} is neither 'apr' nor 'fcgf'")
+    if trainer == "fcgf" and symmetric:
+        raise ValueError("train_and_test: `symmetric` is a switch of APR's recipe")
+    ratio, vs = 4, 0.3
+    t = {}
+    clock = time.perf_counter
+    t0 = clock()
+    s_train, s_test = pair_seeds(n_train, n_test, seed)
+    train = [synthetic_pair(dev, s, n_beams, n_azimuth, k)[0] for s in s_train]
+    held = [synthetic_pair(dev, s, n_beams, n_azimuth, k)[0] for s in s_test]
+    if trainer == "apr":
+        enc, gen, opt = build_models(dev, model, n_out, generator, ratio, lr, symmetric=symmetric)
+        tstep = GenerativePairTrainStep(enc, gen, opt, voxel_size=vs, point_generation_ratio=ratio,
+                                        regularization_strength=0.01 if symmetric else 0.1, loss_ratio=2e-3,
+                                        num_pos_per_batch=num_pos, num_hn_samples_per_batch=num_hn, symmetric=symmetric)
+    else:
+        torch.manual_seed(0)
+        enc = load_model(model)(1, n_out, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=5, D=3).to(dev)
+        opt = torch.optim.SGD(enc.parameters(), lr=lr, momentum=0.8, weight_decay=1e-4)
+        tstep = PairTrainStep(enc, opt, trainer='HardestContrastiveLossTrainer', num_pos_per_batch=num_pos,
+                              num_hn_samples_per_batch=num_hn)
+    torch.cuda.synchronize()
+    t["data"] = clock() - t0
+    t1 = clock()
+    losses = []
+    for it in range(iterations):
+        np.random.seed(it)
+        losses.append(tstep(train[it % n_train])["loss"])
+    losses = [float(v) for v in torch.stack(losses).cpu()] if losses else []
+    t["train"] = clock() - t1
+    t1 = clock()
+    tester = FCGFTestEpoch(enc, variant=trainer, voxel_size=vs, ransac_iters=ransac_iters, subsample_size=subsample_size,
+                           n_points=n_points, rte_thresh=RTE_THRESH, rre_thresh=RRE_THRESH, pairs_per_fetch=pairs_per_fetch)
+    np.random.seed(0)
+    summary, records = tester.epoch(held)
+    t["test"] = clock() - t1
+    t["total"] = clock() - t0
+    return {"losses": losses, "summary": summary, "fmr": fmr_table(records), "records": records, "recall": summary["recall"],
+            "n_replayed": summary["n_replayed"], "train_seeds": s_train, "test_seeds": s_test,
+            "voxels": [int(h["sinput0_C"].shape[0]) for h in held], "ransac_iters": ransac_iters, "seconds": t}

@@ -1798,6 +1798,32 @@ def ransac_decode(raw_host, n0):
     return r[:16].reshape(4, 4).copy(), info
 
 
+def ransac_encode(T, info):
+    """The inverse of `ransac_decode`: (T [4,4] float64, info of `ransac_pose`) -> numpy uint8 raw result whose decoding
+    gives back exactly these figures (the raw form carries the squared error sum, not the rmse: the sum is searched among
+    the neighbours of rmse^2 * inliers until its decoding is the rmse, bit for bit).  Host only."""
+    import struct
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    inliers, rmse = int(info["inliers"]), float(info["rmse"])
+    err2 = rmse * rmse * inliers
+    if inliers > 0:
+        lo = hi = err2
+        for _ in range(64):
+            if np.sqrt(np.float64(lo) / inliers) == rmse or np.sqrt(np.float64(hi) / inliers) == rmse:
+                break
+            lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+        err2 = float(lo if np.sqrt(np.float64(lo) / inliers) == rmse else hi)
+        if np.sqrt(np.float64(err2) / inliers) != rmse:
+            raise _lib.AprHipError("ransac_encode: no squared error sum decodes to this rmse")
+    it = int(info["best_iteration"])
+    raw = struct.pack("<12dqiidq", *T[:3].reshape(12), it, inliers if it >= 0 else -1, 0, err2, int(info["n_valid"]))
+    raw = np.frombuffer(raw, np.uint8).copy()
+    back, binfo = ransac_decode(raw, 1)
+    if back.tobytes() != T.tobytes() or any(binfo[k] != info[k] for k in ("inliers", "rmse", "best_iteration", "n_valid")):
+        raise _lib.AprHipError("ransac_encode: the pose's last row is not 0 0 0 1 or a figure does not survive the raw form")
+    return raw
+
+
 def irls_pose(pts0, pts1, weight=None):
     """est_quad_linear_robust on the GPU -> float32 [4,4] CPU tensor.  Synchronises."""
     pts0 = _f32(pts0, "irls.pts0").contiguous()
@@ -1903,6 +1929,77 @@ def predator_test_pair(s_p, t_p, corr, rot, trans, raw, records, slot, distance_
     check(lib.apr_predator_test_pair(ptr(s_p), s_p.shape[0], ptr(t_p), t_p.shape[0], ptr(corr), ptr(rot), ptr(trans), ptr(raw),
                                      float(distance_threshold), float(inlier_distance_threshold), float(rot_threshold),
                                      float(trans_threshold), ptr(records), records.shape[0], int(slot), stream()))
+
+
+def ransac_pose_async(xyz0, xyz1, corr, max_dist, edge_ratio=0.9, max_iter=4000000, seed=0):
+    """`ransac_pose` enqueued without a host synchronisation, all iterations in a single round -> uint8 device tensor
+    holding the raw result (decode a fetched copy with `ransac_decode`).  Equal to `ransac_pose` whenever
+    n_valid <= 2^20 or max_iter <= 2^20; otherwise the hypothesis list overflowed and the pose is not final
+    (`fcgf_test_pair` flags it in `FTEST_OVERFLOW`): redo such a pair through `ransac_pose`."""
+    xyz0 = _f32(xyz0, "ransac.xyz0").contiguous()
+    xyz1 = _f32(xyz1, "ransac.xyz1").contiguous()
+    if corr.dtype != torch.int64 or not corr.is_cuda or corr.dim() != 1 or corr.shape[0] != xyz0.shape[0]:
+        raise _lib.AprHipError("ransac_pose_async: corr must be an int64 GPU tensor, one entry per source point")
+    corr = corr.contiguous()
+    n0, n1 = xyz0.shape[0], xyz1.shape[0]
+    lib = _lib_()
+    sb = int(lib.apr_ransac_scratch_bytes(n0, int(max_iter)))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=xyz0.device)
+    raw = torch.empty(int(lib.apr_ransac_raw_bytes()), dtype=torch.uint8, device=xyz0.device)
+    check(lib.apr_ransac_pose_async(ptr(xyz0), n0, ptr(xyz1), n1, ptr(corr), float(max_dist), float(edge_ratio),
+                                    int(max_iter), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(scratch), sb, ptr(raw), stream()))
+    return raw
+
+
+FTEST_RECORD_FLOATS = 48      # APR_FCGF_TEST_RECORD_FLOATS
+# columns of an FCGF test record (include/apr_hip.h: apr_fcgf_test_pair); [8, 24) is the row-major 4x4 float32 estimate,
+# [32, 42) the counts of find_corr correspondences closer than k * 0.1, k = 1 .. 10
+FTEST_RTE, FTEST_RRE, FTEST_SUCCESS, FTEST_DIST, FTEST_M0, FTEST_K0, FTEST_K1, FTEST_BAD, FTEST_T = range(9)
+FTEST_INLIERS, FTEST_RMSE, FTEST_N_VALID, FTEST_BEST_ITERATION, FTEST_OVERFLOW = 24, 25, 26, 27, 28
+FTEST_INLIER_EST, FTEST_INLIER_GT, FTEST_HITS, FTEST_HIT_LEVELS = 29, 30, 32, 10
+
+
+def fcgf_test_pair(xyz0, xyz1, nn, r0, r1, corr, T_gt, raw, records, slot, sel0=None, sel1=None, distance_threshold=0.3,
+                   rte_thresh=2, rre_thresh=5, max_iter=4000000, dists=None):
+    """The per-pair figures of FCGF_APR's tester (scripts/test_apr.py:120-186) from the raw RANSAC result `raw` where
+    `ransac_pose_async` left it on the GPU, into `records[slot]` (float64 [pairs, 48] on the GPU, columns `FTEST_*`):
+    find_corr's correspondences are xyz0[sel0] <-> xyz1[sel1[nn]], RANSAC ran on r0 <-> r1[corr] with `max_iter`
+    iterations.  `dists`: optional float32 GPU tensor of len(nn) elements that receives the pair's row of dists_nn.
+    One launch; does not synchronise and returns nothing -- read `records` back when the epoch is over."""
+    xyz0 = _f32(xyz0, "fcgf_test_pair.xyz0").contiguous()
+    xyz1 = _f32(xyz1, "fcgf_test_pair.xyz1").contiguous()
+    r0 = _f32(r0, "fcgf_test_pair.r0").contiguous()
+    r1 = _f32(r1, "fcgf_test_pair.r1").contiguous()
+    T_gt = _f32(T_gt, "fcgf_test_pair.T_gt").contiguous()
+    raw = _dev(raw, torch.uint8, "fcgf_test_pair.raw")
+    for t in (xyz0, xyz1, r0, r1):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise _lib.AprHipError("fcgf_test_pair: the clouds must be [n, 3]")
+    if T_gt.numel() != 16:
+        raise _lib.AprHipError("fcgf_test_pair: T_gt must hold 16 floats")
+    nn, corr = _dev(nn, torch.int64, "fcgf_test_pair.nn"), _dev(corr, torch.int64, "fcgf_test_pair.corr")
+    sel0 = None if sel0 is None else _dev(sel0, torch.int64, "fcgf_test_pair.sel0")
+    sel1 = None if sel1 is None else _dev(sel1, torch.int64, "fcgf_test_pair.sel1")
+    m0 = xyz0.shape[0] if sel0 is None else sel0.numel()
+    m1 = xyz1.shape[0] if sel1 is None else sel1.numel()
+    if nn.dim() != 1 or nn.shape[0] != m0:
+        raise _lib.AprHipError(f"fcgf_test_pair: nn has {nn.numel()} rows for {m0} source rows")
+    if corr.dim() != 1 or corr.shape[0] != r0.shape[0]:
+        raise _lib.AprHipError("fcgf_test_pair: one corr entry per row of r0 expected")
+    if dists is not None:
+        _lib.require_gpu_tensor(dists, torch.float32, "fcgf_test_pair.dists")
+        if dists.numel() != m0 or not dists.is_contiguous():
+            raise _lib.AprHipError(f"fcgf_test_pair: dists must be a contiguous float32 tensor of {m0} elements")
+    lib = _lib_()
+    if raw.numel() < int(lib.apr_ransac_raw_bytes()):
+        raise _lib.AprHipError("fcgf_test_pair: raw is shorter than a raw RANSAC result")
+    _lib.require_gpu_tensor(records, torch.float64, "fcgf_test_pair.records")
+    if records.dim() != 2 or records.shape[1] != FTEST_RECORD_FLOATS or not records.is_contiguous():
+        raise _lib.AprHipError(f"fcgf_test_pair: records must be a contiguous [pairs, {FTEST_RECORD_FLOATS}]")
+    check(lib.apr_fcgf_test_pair(ptr(xyz0), xyz0.shape[0], ptr(xyz1), xyz1.shape[0], ptr(sel0), ptr(sel1), m0, m1, ptr(nn),
+                                 ptr(r0), r0.shape[0], ptr(r1), r1.shape[0], ptr(corr), ptr(T_gt), ptr(raw),
+                                 float(distance_threshold), float(rte_thresh), float(rre_thresh), int(max_iter), ptr(dists),
+                                 ptr(records), records.shape[0], int(slot), stream()))
 
 
 ICP_RECORD_DOUBLES = 20      # APR_ICP_RECORD_DOUBLES

@@ -576,6 +576,14 @@ int apr_ransac_pose_geometric_async(const float* xyz0, int64_t n0, const float* 
                                     int64_t max_validation, uint64_t seed, void* scratch, size_t scratch_bytes,
                                     void* raw_dev, void* stream);
 int apr_ransac_decode(const void* raw_host, double* result_host);
+/* apr_ransac_pose without the host synchronisation: ALL max_iter iterations in a single round (the per-pair body of
+ * apr_match_pose_batch), the raw result copied to `raw_dev`.  Scratch: apr_ransac_scratch_bytes(n0, max_iter).  The
+ * decoded result equals apr_ransac_pose's whenever total_valid <= 2^20 or max_iter <= 2^20; otherwise the hypothesis
+ * list of the single round overflowed, the pose is NOT final and the pair has to be redone through apr_ransac_pose
+ * (apr_fcgf_test_pair's column [28] says so on the device).  Call site: FCGFTestEpoch (apr_amd/fcgf/lib/tester.py). */
+int apr_ransac_pose_async(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int64_t* corr,
+                          double max_dist, double edge_ratio, int64_t max_iter, uint64_t seed, void* scratch,
+                          size_t scratch_bytes, void* raw_dev, void* stream);
 
 /* B independent pairs, matching + pose, in ONE call and ONE host synchronisation: per pair apr_feature_nn_fast
  * (apr_feature_nn for channel counts other than 32/64/128) -> apr_nn_unpack -> single-round RANSAC, enqueued back to
@@ -697,6 +705,41 @@ int apr_predator_test_pair(const float* s_p, int64_t ns, const float* t_p, int64
                            const float* rot_gt, const float* trans_gt, const void* raw_dev, double distance_threshold,
                            double inlier_distance_threshold, double rot_threshold, double trans_threshold,
                            double* records, int64_t n_slots, int64_t slot, void* stream);
+
+/* The record of one tested FCGF pair: what FCGF_APR/scripts/test_apr.py:120-186 and scripts/test_fcgf.py:121-195 compute
+ *   on the host per pair around their RANSAC call (evaluate_nn_dist on find_corr's correspondences, RTE, RRE, the success
+ *   flag, |t_gt|), taken from the RAW RANSAC result on the device (raw_dev: what apr_ransac_pose_async left,
+ *   apr_ransac_raw_bytes() bytes, 8-byte aligned).  One launch of one 1024-thread workgroup, nothing synchronises, integer
+ *   sums in a fixed order.  Call site: FCGFTestEpoch (apr_amd/fcgf/lib/tester.py).  Device pointers:
+ *   xyz0 f32[n0,3], xyz1 f32[n1,3]: the clouds (the collate's pcd0[0], pcd1[0]);
+ *   sel0 i64[m0], sel1 i64[m1]: find_corr's subsample rows, NULL = every row (then m0 == n0 / m1 == n1);
+ *   nn i64[m0]: feature nearest neighbour of subsampled source row i among the m1 subsampled target rows;
+ *   r0 f32[k0,3], r1 f32[k1,3], corr i64[k0]: the point sets RANSAC ran on and their correspondences (test_apr: the clouds
+ *   themselves; test_fcgf: random_sample's rows);  T_gt f32[16] row-major;  dists f32[m0] or NULL.
+ *   Host values: distance_threshold (the RANSAC distance), rte_thresh (metres), rre_thresh_deg, max_iter (of the RANSAC
+ *   call that wrote raw_dev); 0 < m0, k0 < 2^24.
+ * Writes record `slot` of records f64[n_slots, APR_FCGF_TEST_RECORD_FLOATS].  T_ransac is the raw pose rounded to float32
+ *   (`.astype(np.float32)`, test_apr.py:156); [0], [1], [3] are double arithmetic on it and the float32 ground truth:
+ *   [0] RTE = sqrt(sum_a (t_est[a] - t_gt[a])^2), the squares added in the order a = 0, 1, 2
+ *   [1] RRE in radians = arccos((tr - 1) / 2), tr = sum_a (sum_b R_est[a][b] * R_gt[a][b]), each row sum started at 0 and
+ *       added left to right, the rows added in order; unclipped: NaN when the argument leaves [-1, 1] (as apr_valid_pair)
+ *   [2] 1.0 if RTE < rte_thresh && RRE == RRE && RRE < pi / 180 * rre_thresh_deg (both strict, test_apr.py:177), else 0.0
+ *   [3] |t_gt|   [4] m0   [5] k0   [6] k1
+ *   [7] sel0 / sel1 / nn / corr entries out of range: such an entry reads row 0 and is counted
+ *   [8..23] T_ransac, row-major 4x4, widened      [24] inliers   [25] rmse   [26] total_valid   [27] best iteration
+ *   [28] 1.0 if total_valid > 2^20 && max_iter > 2^20 (the single round overflowed: the pose is not final), else 0.0
+ *   [29] share of the k0 correspondences with |R_est r0[i] + t_est - r1[corr[i]]| < distance_threshold, in the float32
+ *        arithmetic of apr_inlier_ratio's 'wo' leg      [30] the same under the ground truth      [31] 0
+ *   [32..41] how many of the m0 find_corr correspondences have (double)d_i < k * 0.1, k = 1 .. 10, where
+ *        d_i = sqrt(|R_gt x0 + t_gt - x1|^2 + 1e-6) in float32 (evaluate_nn_dist, test_apr.py:64-67) and k * 0.1 is the
+ *        double product (0.30000000000000004 for k = 3), as the tables at test_apr.py:200-213 form it      [42..47] 0
+ *   dists, when not NULL, receives the d_i: the pair's row of dists_nn. */
+#define APR_FCGF_TEST_RECORD_FLOATS 48
+int apr_fcgf_test_pair(const float* xyz0, int64_t n0, const float* xyz1, int64_t n1, const int64_t* sel0,
+                       const int64_t* sel1, int64_t m0, int64_t m1, const int64_t* nn, const float* r0, int64_t k0,
+                       const float* r1, int64_t k1, const int64_t* corr, const float* T_gt, const void* raw_dev,
+                       double distance_threshold, double rte_thresh, double rre_thresh_deg, int64_t max_iter,
+                       float* dists, double* records, int64_t n_slots, int64_t slot, void* stream);
 
 /* Hardest-contrastive mining (forward), replaces the mining + masking + loss arithmetic of
  *   contrastive_hardest_negative_loss (FCGF_APR/lib/trainer.py:400-452, `_hash` util/misc.py:6-18).
