@@ -72,7 +72,9 @@ int64_t apr_hash_capacity(int64_t n);
 size_t apr_map_scratch_bytes(int64_t n);
 
 /* xyz f32[n,3] -> coords i32[n,4] = (batch, floor(x/vs), floor(y/vs), floor(z/vs)),
- * fp32 division exactly as `xyz / voxel_size` on a float32 array. */
+ * fp32 division exactly as `xyz / voxel_size` on a float32 array: correctly rounded, denormal quotients kept
+ * (a tiny negative x gives -1, -0.0 gives 0).  Every finite value whose quotient fits an int32 has a defined result,
+ * in or out of the key range (apr_map_build reports the latter); inf and NaN have none. */
 int apr_voxelize(const float* xyz, int64_t n, float voxel_size, int32_t batch,
                  int32_t* coords, void* stream);
 
@@ -88,6 +90,9 @@ int apr_voxelize(const float* xyz, int64_t n, float voxel_size, int32_t batch,
  *                          (== `index` of sparse_quantize(return_index=True)).
  *   n_out      i32[1]      device counter; read it back after a stream sync.
  *   status     i32[1]      device flag, set non-zero on key overflow (APR_ERANGE).
+ * A live row outside the key range (batch < 0 or >= 1023, a floored x / y / z outside [-2^17, 2^17)) sets status and
+ * belongs to no voxel; the rows in range still form the map they would form without it.  Rows at or past *n_dev are
+ * never read: they may hold anything.  Rows of out_coords / out_first at or past *n_out are unspecified.
  */
 int apr_map_build(const int32_t* coords_in, int64_t n, const int32_t* n_dev, int32_t floor_to,
                   uint64_t* keys, int32_t* vals, int64_t cap,
@@ -143,7 +148,9 @@ int apr_segment_counts(const int64_t* out_first, const int32_t* n_dev, const int
  *   or -1.  offset(o) enumerates {-h..h}^3 x fastest.  scale = +ts_in for a
  *   regular / strided conv; for a transposed conv pass the FINE map as
  *   out_coords, the COARSE table as the input table and scale = -ts_fine.
- *   n_out_dev (nullable): device row count, rows >= *n_out_dev are skipped.
+ *   A probed coordinate outside the key range ([-2^17, 2^17) per axis) is no row: -1, whatever its packed key
+ *   would alias (the row across the range edge, the next batch index, the empty-slot sentinel).
+ *   n_out_dev (nullable): device row count, rows >= *n_out_dev are skipped (their nbr entries are left untouched).
  *   replaces ME's kernel-map generation behind MinkowskiConvolution /
  *   MinkowskiConvolutionTranspose (FCGF_APR/model/resunet.py:31-140).
  */

@@ -117,10 +117,12 @@ def kernel_map(in_coords, out_coords, kernel_size, ts_in):
     for o, off in enumerate(offs):
         q = oc.copy()
         q[:, 1:] += off
+        # a probe that leaves the key range finds nothing: packed, it would carry into the next field and alias a real row
+        ok = ((q[:, 1:] >= -_H) & (q[:, 1:] < _H)).all(1)
         kq = pack_keys(q)
         pos = np.searchsorted(ks, kq)
         pos = np.minimum(pos, len(ks) - 1)
-        hit = ks[pos] == kq
+        hit = ok & (ks[pos] == kq)
         nbr[hit, o] = order[pos[hit]]
     return nbr
 
