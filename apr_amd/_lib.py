@@ -215,6 +215,9 @@ PROTOTYPES = {
     "apr_knn": (C.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "apr_row_sums": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "apr_kpconv_weighted": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _p]),
+    "apr_kpconv_fused_ok": (_i32, [_i32, _i32, _i32]),
+    "apr_kpconv_fused_route": (_i32, [_i64, _i32, _i32, _i32]),
+    "apr_kpconv_fused": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i32, _p, _i64, _p]),
     "apr_kpconv_dfeat": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _p]),
     "apr_kpconv_dfeat_contrib": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _p]),
     "apr_reverse_table_scratch_bytes": (_sz, [_i64, _i32, _i64]),
@@ -284,7 +287,8 @@ class KpResnetDesc(C.Structure):
                 ("w_unary1", _p), ("w_kpconv", _p), ("w_unary2", _p), ("w_shortcut", _p),
                 ("seg_in", _p), ("seg_out", _p),
                 ("out", _p), ("ldo", _i64),
-                ("scratch", _p), ("scratch_bytes", _sz)]
+                ("scratch", _p), ("scratch_bytes", _sz),
+                ("kpconv_route", _i32)]
 
 
 _lib = None

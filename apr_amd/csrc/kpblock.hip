@@ -78,6 +78,10 @@ APR_API int apr_kp_resnet_block(const apr_kp_resnet_desc* dp, void* stream) {
   APR_CHECK_ARG((d.w_shortcut != nullptr) == (d.in_dim != d.out_dim), "apr_kp_resnet_block: shortcut Linear exists iff in_dim != out_dim");
   APR_CHECK_ARG(d.strided || d.n_in == d.n_out, "apr_kp_resnet_block: a same-level block maps n_in rows to n_in rows");
   APR_CHECK_ARG(d.nseg <= 1 || (d.seg_in && d.seg_out), "apr_kp_resnet_block: segment offsets missing");
+  APR_CHECK_ARG(d.kpconv_route == 0 || d.kpconv_route == 1, "apr_kp_resnet_block: kpconv_route must be 0 or 1");
+  APR_CHECK_ARG(d.kpconv_route == 0 || (d.n_kp == 15 && apr_kpconv_fused_ok(d.mid, d.mid, d.H)),
+                "apr_kp_resnet_block: kpconv_route 1 needs a shape that apr_kpconv_fused_ok takes (mid %d, H %d, n_kp %d)", d.mid, d.H,
+                d.n_kp);
   AprArena arena(d.scratch);
   const KpCarve c = kp_walk(arena, d);
   APR_CHECK_ARG(arena.fits(d.scratch_bytes), "apr_kp_resnet_block: scratch too small");
@@ -98,10 +102,17 @@ APR_API int apr_kp_resnet_block(const apr_kp_resnet_desc* dp, void* stream) {
   // 2. KPConv: kernel-point correlation, then [n_out, 15 mid] x [15 mid, mid]
   const int32_t kk = d.n_kp * d.mid;
   KP_TRY(apr_row_sums(x1, ldx1, d.n_in, d.mid, c.rs, stream));
-  KP_TRY(apr_kpconv_weighted(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp, d.extent,
-                             c.rs, c.wf, kk, stream));
-  // 3. ... + InstanceNorm + LeakyReLU
-  KP_TRY(kp_linear_norm(d, c, c.wf, kk, d.n_out, kk, d.mid, d.w_kpconv, nullptr, 0, true, c.kp, d.mid, d.seg_out, stream));
+  if (d.kpconv_route == 1) {
+    // both steps in one kernel, the weighted features never leave the CU (c.wf stays unused); 3. InstanceNorm + LeakyReLU
+    KP_TRY(apr_kpconv_fused(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp, d.extent, c.rs,
+                            d.w_kpconv, d.mid, c.kp, d.mid, stream));
+    KP_TRY(kp_norm(d, c, c.kp, d.n_out, d.mid, nullptr, 0, true, c.kp, d.mid, d.seg_out, stream));
+  } else {
+    KP_TRY(apr_kpconv_weighted(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp, d.extent,
+                               c.rs, c.wf, kk, stream));
+    // 3. ... + InstanceNorm + LeakyReLU
+    KP_TRY(kp_linear_norm(d, c, c.wf, kk, d.n_out, kk, d.mid, d.w_kpconv, nullptr, 0, true, c.kp, d.mid, d.seg_out, stream));
+  }
   // 4. shortcut: max-pool over the pooling table when strided, Linear + InstanceNorm when the widths differ
   const float* sc = d.x;
   int64_t ldsc = d.ldx;

@@ -215,6 +215,37 @@ def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent):
     return wf
 
 
+def rows_aligned(x, c):
+    """float32 GPU matrix of `c` columns whose rows start on 16-byte boundaries (what apr_kpconv_fused reads)"""
+    return bool(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == c
+                and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
+
+
+def kpconv_fused(q_pts, s_pts, nbr, x, kernel_points, extent, w_info, out=None):
+    """Rigid KPConv forward in one kernel (apr_kpconv_fused): correlation and contraction, the weighted features never
+    reach memory.  `w_info`: `pack_linear` of W.reshape(15 * cin, cout) (its bf16-split image is read).  Forward only;
+    shapes and layouts the kernel does not take raise (the callers fall back, not this wrapper)."""
+    nbr = _i32(nbr, "kpconv_fused.nbr")
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise _lib.AprHipError("kpconv_fused.x: need a float32 GPU matrix with unit column stride")
+    if not (q_pts.is_cuda and s_pts.is_cuda and kernel_points.is_cuda):
+        raise _lib.AprHipError("kpconv_fused: the points and the kernel points must be GPU tensors")
+    _, cin, cout, cin_p, cout_p, w_bf3 = w_info
+    nq, ns = q_pts.shape[0], s_pts.shape[0]
+    n_kp = kernel_points.shape[0]
+    if w_bf3 is None or cin_p != cin or cout_p != cout or cin != n_kp * x.shape[1]:
+        raise _lib.AprHipError("kpconv_fused: the weights need a bf16-split image of [15 * cin, cout]")
+    if out is None:
+        out = torch.empty((nq, cout), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (nq, cout) and out.stride(1) == 1):
+        raise _lib.AprHipError("kpconv_fused.out: need a float32 GPU [nq, cout] matrix with unit column stride")
+    rs = row_sums(x)
+    check(_lib.load().apr_kpconv_fused(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1], ptr(x),
+                                       x.stride(0), x.shape[1], ptr(kernel_points.contiguous()), n_kp, float(extent), ptr(rs),
+                                       ptr(w_bf3), cout, ptr(out), out.stride(0), stream()))
+    return out
+
+
 _REV_CACHE = {}     # (data_ptr, shape, version, ns) -> (nbr tensor kept alive, rev_t, start): one build per neighbour table
 
 

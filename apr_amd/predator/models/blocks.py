@@ -24,6 +24,9 @@ from ..kernels.kernel_points import load_kernels
 
 FUSED_BLOCK = os.environ.get("APR_KP_FUSED_BLOCK", "1") != "0"     # A/B switch: 0 = one library call per op of a block
 KPCONV_TRAIN_HIP = os.environ.get("APR_KPCONV_TRAIN_HIP", "1") != "0"   # A/B switch: 0 = KPConv's training path on torch ops
+# the fused KPConv forward (apr_kpconv_fused): 0 = never, 1 = where apr_kpconv_fused_route says so, 2 = wherever it can run
+FUSED_KPCONV = int(os.environ.get("APR_KPCONV_FUSED", "0") or 0)
+KPCONV_ROUTE_HOOK = None     # set to a callable(KPConv module, nq, cin, cout, H) to observe every fused-route decision
 _SEG_ARRAYS = {}
 
 
@@ -84,6 +87,19 @@ class KPConv(nn.Module):
             self._key = key
         return self._packed
 
+    def _fused_route(self, nq, H, aligned):
+        """Does the fused kernel take this layer?  FUSED_KPCONV, the kernel's shapes, `aligned` (float32 GPU rows of
+        in_channels features on 16-byte boundaries) and, at FUSED_KPCONV = 1, the measured route table."""
+        if not FUSED_KPCONV or self.K != 15 or nq <= 0 or not aligned or not kp_ops.DENSE_BF3:
+            return False
+        lib = _lib.load()
+        if not lib.apr_kpconv_fused_ok(self.in_channels, self.out_channels, int(H)):
+            return False
+        take = FUSED_KPCONV >= 2 or bool(lib.apr_kpconv_fused_route(int(nq), self.in_channels, self.out_channels, int(H)))
+        if take and KPCONV_ROUTE_HOOK is not None:
+            KPCONV_ROUTE_HOOK(self, int(nq), self.in_channels, self.out_channels, int(H))
+        return take
+
     def forward(self, q_pts, s_pts, neighb_inds, x):
         if kp_ops.tracking(x, self.weights):
             # training: forward and both gradients on the HIP kernels (SURVEY 8(f) next-3).  The input gradient needs
@@ -99,6 +115,9 @@ class KPConv(nn.Module):
         if prof is not None:      # bench.py roofline leg: HIP events on the launch stream around the layer's kernels
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
+        elif self._fused_route(q_pts.shape[0], neighb_inds.shape[1], kp_ops.rows_aligned(x, self.in_channels)) \
+                and self._weight()[5] is not None:
+            return kp_ops.kpconv_fused(q_pts, s_pts, neighb_inds, x, self.kernel_points, self.KP_extent, self._weight())
         wf = kp_ops.kpconv_weighted(q_pts, s_pts, neighb_inds, x, self.kernel_points, self.KP_extent)
         out = kp_ops.linear(wf, self._weight())
         if prof is not None:
@@ -304,6 +323,8 @@ class ResnetBottleneckBlock(nn.Module):
         if out is None:
             out = torch.empty((n_out, self.out_dim), dtype=torch.float32, device=features.device)
         d.out, d.ldo = out.data_ptr(), out.stride(0)
+        # the KPConv reads unary1's [n_in, mid] rows in the scratch arena, or `features` itself (aligned: _fused_ok)
+        d.kpconv_route = int(self.KPConv._fused_route(n_out, inds.shape[1], True))
         sb = int(lib.apr_kp_resnet_scratch_bytes(C.byref(d)))
         scratch = torch.empty(sb, dtype=torch.uint8, device=features.device)
         d.scratch, d.scratch_bytes = scratch.data_ptr(), sb

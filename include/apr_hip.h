@@ -944,6 +944,8 @@ typedef struct apr_kp_resnet_desc {
   const int64_t* seg_in; const int64_t* seg_out;
   float* out; int64_t ldo;
   void* scratch; size_t scratch_bytes;
+  int32_t kpconv_route;      /* 0: apr_kpconv_weighted + the dense GEMM; 1: apr_kpconv_fused + InstanceNorm (the wf region of the
+                              * scratch stays unused; a shape apr_kpconv_fused_ok rejects is an argument error) */
 } apr_kp_resnet_desc;
 size_t apr_kp_resnet_scratch_bytes(const apr_kp_resnet_desc* desc);
 int apr_kp_resnet_block(const apr_kp_resnet_desc* desc, void* stream);
@@ -966,6 +968,19 @@ int apr_row_sums(const float* x, int64_t ld, int64_t n, int32_t c, float* out, v
 int apr_kpconv_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
                         int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
                         int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream);
+/* Both steps of the rigid KPConv in ONE kernel (kpconv_fused.hip): out[q, :] = wf[q, :] @ W.reshape(15 cin, cout) with wf as
+ * apr_kpconv_weighted defines it; the [queries, 15 cin] tile lives in LDS and registers only.  Correlation in fp32 on the
+ * fp32 MFMA, contraction on the bf16 MFMA in the 3-way split (six cross terms, fp32 accumulate), no atomics: the same bits
+ * on every run.  w_bf3: apr_spconv_pack_weights_bf3(W[15 cin, cout], K = 1) -- the image apr_dense_gemm_bf3 reads.  rowsum:
+ * apr_row_sums of x.  apr_kpconv_fused_ok (host only): n_kp = 15, cin and cout multiples of 64 in 64 .. 512, 1 <= H <= 128.
+ * apr_kpconv_fused also needs ldx % 4 == 0, ldo % 4 == 0 and x / out / w_bf3 16-byte aligned; everything else is refused
+ * before any launch (no fallback inside).  nq == 0 launches nothing; columns of out behind cout are never written.
+ * apr_kpconv_fused_route (host only): 1 for the shapes where the fused kernel measured faster than the two launches. */
+int32_t apr_kpconv_fused_ok(int32_t cin, int32_t cout, int32_t H);
+int32_t apr_kpconv_fused_route(int64_t nq, int32_t cin, int32_t cout, int32_t H);
+int apr_kpconv_fused(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                     const float* x, int64_t ldx, int32_t cin, const float* kernel_points, int32_t n_kp, float extent,
+                     const float* rowsum, const void* w_bf3, int32_t cout, float* out, int64_t ldo, void* stream);
 /* Backward of apr_kpconv_weighted with respect to the neighbour features (training path, SURVEY 8(f) next-3;
  * Predator_APR/models/blocks.py:326-374 through lib/trainer.py:142-280): dx[nbr[q,h], c] += (1 / num_q) * sum_k
  * w[q,k,h] * dwf[q, k*cin + c] with float atomics (dx must be zero-initialised; f32 [ns, cin]).  The weight gradient of
