@@ -335,6 +335,98 @@ class KPConvFunction(torch.autograd.Function):
         return None, None, None, dx, dw, None, None
 
 
+def deform_ok(x, cin, H, K=15):
+    """Shapes and layouts the deformable kernels take (apr_kpconv_deform_*): 15 kernel points, cin a multiple of 64 up to
+    512, 1 <= H <= 128, float32 GPU rows on 16-byte boundaries.  Everything else runs the torch formulation."""
+    return K == 15 and cin % 64 == 0 and 64 <= cin <= 512 and 1 <= H <= 128 and rows_aligned(x, cin)
+
+
+def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=True):
+    """Deformable KPConv step 1 (apr_kpconv_deform_weighted) -> (wf [nq, 15 * cin], min_d2 [nq, 15] or None).
+    dkp [nq, 15, 3]: the query's own kernel points; mod [nq, 15] or None; wf is already mod / (in-range count)."""
+    nbr = _i32(nbr, "kpconv_deform.nbr")
+    x, ldx = ops._rows(x, "kpconv_deform.x")
+    nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
+    if tuple(dkp.shape) != (nq, 15, 3) or (mod is not None and tuple(mod.shape) != (nq, 15)):
+        raise _lib.AprHipError("kpconv_deform: dkp must be [nq, 15, 3] and mod [nq, 15]")
+    dkp = dkp.detach().to(torch.float32).contiguous()
+    mod = None if mod is None else mod.detach().to(torch.float32).contiguous()
+    wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=x.device)
+    md = torch.empty((nq, 15), dtype=torch.float32, device=x.device) if want_min_d2 else None
+    rs = row_sums(x)
+    check(_lib.load().apr_kpconv_deform_weighted(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
+                                                 nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent), ptr(rs),
+                                                 ptr(wf), wf.stride(0), ptr(md), stream()))
+    return wf, md
+
+
+class KPConvDeformFunction(torch.autograd.Function):
+    """Deformable / modulated KPConv (blocks.py:229-374) on the HIP kernels, given the query's kernel points dkp
+    [nq, 15, 3] and modulations mod [nq, 15] (or None): returns (out, min_d2).
+    forward   wf = apr_kpconv_deform_weighted, out = wf @ W (dense MFMA GEMM); min_d2 is not differentiable (nothing in the
+              reference differentiates it);
+    d W       = wf^T @ dout (apr_spconv_wgrad; wf recomputed);
+    d x       = apr_kpconv_deform_dfeat_contrib + apr_reverse_gather_range in DX_CHUNK_BYTES chunks (deterministic);
+    d dkp, d mod = apr_kpconv_deform_dgeom.
+    The in-range count is a constant of the graph.  The points and the neighbour table get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q_pts, s_pts, inds, x, weights, dkp, mod, extent):
+        inds = _i32(inds, "kpconv_deform.nbr")
+        x = x.contiguous()
+        K, cin, cout = weights.shape
+        wf, md = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, extent)
+        out = linear(wf, pack_linear(weights.detach().reshape(K * cin, cout), bf3=False))
+        ctx.save_for_backward(q_pts, s_pts, inds, x, weights, dkp, mod)
+        ctx.extent = float(extent)
+        ctx.mark_non_differentiable(md)
+        return out, md
+
+    @staticmethod
+    def backward(ctx, dout, _dmin):
+        q_pts, s_pts, inds, x, weights, dkp, mod = ctx.saved_tensors
+        K, cin, cout = weights.shape
+        dout = dout.contiguous()
+        dx = dw = ddkp = dmod = None
+        if ctx.needs_input_grad[4]:
+            wf, _ = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, ctx.extent, want_min_d2=False)
+            dw = ops.spconv_wgrad(wf, dout, None, 1, wf.shape[1], cout)[0].reshape(K, cin, cout)
+        need_geom = ctx.needs_input_grad[5] or (mod is not None and ctx.needs_input_grad[6])
+        if ctx.needs_input_grad[3] or need_geom:
+            dwf = linear(dout, pack_linear(weights.detach().reshape(K * cin, cout).t().contiguous(), bf3=False))
+            dwf, lddwf = ops._rows(dwf, "kpconv_deform.dwf")
+            rs = row_sums(x)
+            lib = _lib.load()
+            nq, H, ns = q_pts.shape[0], inds.shape[1], s_pts.shape[0]
+            qp, sp = q_pts.contiguous(), s_pts.contiguous()
+            kd = dkp.detach().contiguous()
+            md = None if mod is None else mod.detach().contiguous()
+            if ctx.needs_input_grad[3]:
+                if nq * H >= (1 << 31):
+                    raise _lib.AprHipError("kpconv_deform: neighbour table too large for the reverse table")
+                rev_t, start = reverse_table(inds, ns)
+                qc = max(1, min(nq, DX_CHUNK_BYTES // max(1, H * cin * 4)))
+                contrib = torch.empty((min(nq, qc) * H, cin), dtype=torch.float32, device=x.device)
+                dx = torch.empty_like(x)
+                for q0 in range(0, nq, qc):
+                    q1 = min(nq, q0 + qc)
+                    check(lib.apr_kpconv_deform_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                              ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
+                                                              ptr(None if md is None else md[q0:q1]), 15, ctx.extent, ptr(rs),
+                                                              ptr(contrib), stream()))
+                    check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
+                                                       int(q0 > 0), ptr(dx), dx.stride(0), stream()))
+            if need_geom:
+                ddkp = torch.empty((nq, 15, 3), dtype=torch.float32, device=x.device)
+                dmod = torch.empty((nq, 15), dtype=torch.float32, device=x.device)
+                check(lib.apr_kpconv_deform_dgeom(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin, ptr(dwf),
+                                                  lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp), ptr(dmod),
+                                                  stream()))
+                if mod is None:
+                    dmod = None
+        return None, None, None, dx, dw, ddkp, dmod, None
+
+
 def gather_pool(x, inds, mode, out=None):
     """mode 'max' -> max_pool(x, inds); 'closest' -> closest_pool(x, inds).  `out`: a [nq, c] column slice to write into."""
     inds = _i32(inds, "gather_pool.inds")

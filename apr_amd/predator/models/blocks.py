@@ -4,8 +4,9 @@ Module names, constructor arguments and parameter names follow
 /root/reference/Predator_APR/models/blocks.py (KPConv :134-379, BatchNormBlock :436-474,
 UnaryBlock :477-510, LastUnaryBlock :513-536, SimpleBlock :539-593, ResnetBottleneckBlock :596-681,
 NearestUpsampleBlock :697-712, MaxPoolBlock :715-726, block_decider :385-433), so a reference
-state_dict loads unchanged.  Only the rigid KPConv the APR configs use is implemented
-(KP_influence 'linear', aggregation 'sum', not deformable); other settings raise.
+state_dict loads unchanged.  KPConv is implemented for KP_influence 'linear' and aggregation 'sum' (other settings raise),
+rigid and deformable / modulated (blocks.py:235-316: a rigid offset_conv moves the 15 kernel points of every query and,
+when modulated, scales their features; kernels in csrc/kpconv_deform.hip).
 Inference runs the HIP kernels; when autograd is recording (training) every block switches
 to differentiable torch ops with the reference's formulation — KPConv backward kernels are a later round.
 """
@@ -24,6 +25,7 @@ from ..kernels.kernel_points import load_kernels
 
 FUSED_BLOCK = os.environ.get("APR_KP_FUSED_BLOCK", "1") != "0"     # A/B switch: 0 = one library call per op of a block
 KPCONV_TRAIN_HIP = os.environ.get("APR_KPCONV_TRAIN_HIP", "1") != "0"   # A/B switch: 0 = KPConv's training path on torch ops
+KPCONV_DEFORM_HIP = os.environ.get("APR_KPCONV_DEFORM_HIP", "1") != "0"   # A/B switch: 0 = the deformed convolution on torch ops
 # the fused KPConv forward (apr_kpconv_fused): 0 = never, 1 = where apr_kpconv_fused_route says so, 2 = wherever it can run
 FUSED_KPCONV = int(os.environ.get("APR_KPCONV_FUSED", "0") or 0)
 KPCONV_ROUTE_HOOK = None     # set to a callable(KPConv module, nq, cin, cout, H) to observe every fused-route decision
@@ -61,19 +63,37 @@ class KPConv(nn.Module):
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius, fixed_kernel_points='center',
                  KP_influence='linear', aggregation_mode='sum', deformable=False, modulated=False):
         super().__init__()
-        if deformable or modulated or KP_influence != 'linear' or aggregation_mode != 'sum':
-            raise NotImplementedError("HIP KPConv: rigid / linear influence / sum aggregation only (the APR configs)")
+        if KP_influence != 'linear' or aggregation_mode != 'sum':
+            raise NotImplementedError("HIP KPConv: linear influence / sum aggregation only (the APR configs)")
         self.K, self.p_dim = kernel_size, p_dim
         self.in_channels, self.out_channels = in_channels, out_channels
         self.radius, self.KP_extent = radius, KP_extent
         self.fixed_kernel_points = fixed_kernel_points
+        self.KP_influence, self.aggregation_mode = KP_influence, aggregation_mode
+        self.deformable, self.modulated = deformable, modulated     # `modulated` on a rigid layer is ignored (blocks.py:357)
+        # set on every forward of a deformable layer, as the reference does (blocks.py:170-172, 238, 279, 295); min_d2 is
+        # stored DETACHED: nothing in the reference differentiates it
+        self.min_d2 = self.deformed_KP = self.offset_features = None
         self.weights = Parameter(torch.zeros((self.K, in_channels, out_channels), dtype=torch.float32),
                                  requires_grad=True)
-        kaiming_uniform_(self.weights, a=math.sqrt(5))
+        if deformable:      # blocks.py:179-193: a rigid KPConv produces 3 (+ 1 when modulated) values per kernel point
+            self.offset_dim = (self.p_dim + 1) * self.K if modulated else self.p_dim * self.K
+            self.offset_conv = KPConv(self.K, self.p_dim, in_channels, self.offset_dim, KP_extent, radius,
+                                      fixed_kernel_points=fixed_kernel_points, KP_influence=KP_influence,
+                                      aggregation_mode=aggregation_mode)
+            self.offset_bias = Parameter(torch.zeros(self.offset_dim, dtype=torch.float32), requires_grad=True)
+        else:
+            self.offset_dim = self.offset_conv = self.offset_bias = None
+        self.reset_parameters()      # after offset_conv drew its own weights: the reference's order of random draws
         self.kernel_points = Parameter(torch.tensor(load_kernels(self.radius, self.K, dimension=self.p_dim,
                                                                  fixed=self.fixed_kernel_points),
                                                     dtype=torch.float32), requires_grad=False)
         self._packed, self._key = None, None
+
+    def reset_parameters(self):
+        kaiming_uniform_(self.weights, a=math.sqrt(5))
+        if self.deformable:
+            nn.init.zeros_(self.offset_bias)
 
     def _weight(self):
         key = _param_key(self.weights)
@@ -90,7 +110,7 @@ class KPConv(nn.Module):
     def _fused_route(self, nq, H, aligned):
         """Does the fused kernel take this layer?  FUSED_KPCONV, the kernel's shapes, `aligned` (float32 GPU rows of
         in_channels features on 16-byte boundaries) and, at FUSED_KPCONV = 1, the measured route table."""
-        if not FUSED_KPCONV or self.K != 15 or nq <= 0 or not aligned or not kp_ops.DENSE_BF3:
+        if not FUSED_KPCONV or self.deformable or self.K != 15 or nq <= 0 or not aligned or not kp_ops.DENSE_BF3:
             return False
         lib = _lib.load()
         if not lib.apr_kpconv_fused_ok(self.in_channels, self.out_channels, int(H)):
@@ -101,6 +121,8 @@ class KPConv(nn.Module):
         return take
 
     def forward(self, q_pts, s_pts, neighb_inds, x):
+        if self.deformable:
+            return self._forward_deformable(q_pts, s_pts, neighb_inds, x)
         if kp_ops.tracking(x, self.weights):
             # training: forward and both gradients on the HIP kernels.  The input gradient needs
             # 64-channel multiples (apr_kpconv_dfeat); the first layer (cin = 1) reads the constant input features, which
@@ -134,6 +156,54 @@ class KPConv(nn.Module):
         nx = kp_ops.gather_pad(x, inds)                                              # [n, h, cin]
         weighted = torch.matmul(w, nx).permute(1, 0, 2)                              # [k, n, cin]
         out = torch.sum(torch.matmul(weighted, self.weights), dim=0)
+        num = torch.sum(torch.gt(torch.sum(nx, dim=-1), 0.0), dim=-1)
+        return out / torch.max(num, torch.ones_like(num)).unsqueeze(1)
+
+    def _forward_deformable(self, q_pts, s_pts, inds, x):
+        """blocks.py:235-262 (offsets and modulations from the rigid offset_conv: elementwise glue on torch ops), then the
+        deformed convolution on apr_kpconv_deform_* inside the kernels' limits (kp_ops.deform_ok), in inference and in
+        training; every other shape, and APR_KPCONV_DEFORM_HIP=0, takes the torch formulation."""
+        of = self.offset_conv(q_pts, s_pts, inds, x) + self.offset_bias
+        self.offset_features = of
+        n3 = self.p_dim * self.K
+        if self.modulated:
+            unscaled = of[:, :n3].view(-1, self.K, self.p_dim)
+            mod = 2 * torch.sigmoid(of[:, n3:])
+        else:
+            unscaled, mod = of.view(-1, self.K, self.p_dim), None
+        dkp = unscaled * self.KP_extent + self.kernel_points
+        self.deformed_KP = dkp
+        tracked = kp_ops.tracking(x, self.weights, of)
+        if x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and not kp_ops.rows_aligned(x, self.in_channels):
+            x = x.contiguous()
+        if KPCONV_DEFORM_HIP and self.p_dim == 3 and kp_ops.deform_ok(x, self.in_channels, inds.shape[1], self.K) \
+                and q_pts.shape[0] > 0 and (not tracked or self.out_channels % 32 == 0):
+            if tracked:
+                out, self.min_d2 = kp_ops.KPConvDeformFunction.apply(q_pts, s_pts, inds, x, self.weights, dkp, mod,
+                                                                     self.KP_extent)
+                return out
+            wf, self.min_d2 = kp_ops.kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, self.KP_extent)
+            return kp_ops.linear(wf, self._weight())
+        return self._forward_autograd_deformable(q_pts, s_pts, inds, x, dkp, mod)
+
+    def _forward_autograd_deformable(self, q_pts, s_pts, inds, x, dkp, mod):
+        """blocks.py:264-374 for a deformable layer with plain torch ops.  The reference's topk re-gather (:301-316) is a
+        mask here: an out-of-range neighbour has zero influence either way, and is not counted.  sqrt is taken of
+        max(d2, 1e-30), so a neighbour exactly on a kernel point gives that kernel point a zero geometry gradient, as
+        the kernels do (the reference's graph gives NaN there)."""
+        ns = s_pts.shape[0]
+        idx = torch.where((inds >= 0) & (inds < ns), inds, torch.full_like(inds, ns)).long()
+        s_pad = torch.cat((s_pts, torch.zeros_like(s_pts[:1]) + 1e6), 0)
+        neighbors = s_pad[idx] - q_pts.unsqueeze(1)                                  # [n, h, 3]
+        sq = torch.sum((neighbors.unsqueeze(2) - dkp.unsqueeze(1)) ** 2, dim=3)        # [n, h, k]
+        self.min_d2 = torch.min(sq, dim=1)[0].detach()
+        in_range = torch.any(sq < self.KP_extent ** 2, dim=2) & (idx < ns)             # [n, h]
+        w = torch.clamp(1 - torch.sqrt(torch.clamp(sq, min=1e-30)) / self.KP_extent, min=0.0).transpose(1, 2)
+        nx = torch.cat((x, torch.zeros_like(x[:1])), 0)[idx] * in_range.unsqueeze(2).to(x.dtype)
+        weighted = torch.matmul(w, nx)                                               # [n, k, cin]
+        if mod is not None:
+            weighted = weighted * mod.unsqueeze(2)
+        out = torch.sum(torch.matmul(weighted.permute(1, 0, 2), self.weights), dim=0)
         num = torch.sum(torch.gt(torch.sum(nx, dim=-1), 0.0), dim=-1)
         return out / torch.max(num, torch.ones_like(num)).unsqueeze(1)
 
@@ -281,7 +351,7 @@ class ResnetBottleneckBlock(nn.Module):
     def _fused_ok(self, features, inds):
         """One library call for the whole block (apr_kp_resnet_block): inference, InstanceNorm blocks, widths that the
         bf16-split dense GEMM takes, rows 16-byte aligned.  APR_KP_FUSED_BLOCK=0 keeps the module-by-module path."""
-        return (FUSED_BLOCK and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
+        return (FUSED_BLOCK and not self.KPConv.deformable and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
                 and kp_ops.DENSE_BF3 and self.in_dim % 64 == 0 and self.out_dim % 256 == 0 and features.is_cuda
                 and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1
                 and features.stride(0) % 4 == 0 and features.data_ptr() % 16 == 0 and inds.dtype == torch.int32
@@ -382,14 +452,14 @@ def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
             return LastUnaryBlock(in_dim, config.point_generation_ratio * 3, config.use_batch_norm,
                                   config.batch_norm_momentum)
         return LastUnaryBlock(in_dim, config.final_feats_dim + 2, config.use_batch_norm, config.batch_norm_momentum)
-    if block_name in ['simple', 'simple_strided']:
+    if block_name in ['simple', 'simple_strided', 'simple_deformable', 'simple_deformable_strided']:
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
-    if block_name in ['resnetb', 'resnetb_strided']:
+    if block_name in ['resnetb', 'resnetb_strided', 'resnetb_deformable', 'resnetb_deformable_strided']:
         return ResnetBottleneckBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
     if block_name in ('max_pool', 'max_pool_wide'):
         return MaxPoolBlock(layer_ind)
     if block_name == 'nearest_upsample':
         return NearestUpsampleBlock(layer_ind)
-    if any(t in block_name for t in ('deformable', 'invariant', 'equivariant', 'global')):
+    if any(t in block_name for t in ('invariant', 'equivariant', 'global')):
         raise NotImplementedError(f"block '{block_name}' is not used by the APR configs")
     raise ValueError('Unknown block name in the architecture definition : ' + block_name)

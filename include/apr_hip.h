@@ -997,6 +997,38 @@ int apr_kpconv_dfeat(const float* q_pts, int64_t nq, const float* s_pts, int64_t
 int apr_kpconv_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
                              const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
                              float extent, const float* rowsum, float* contrib, void* stream);
+/* Deformable / modulated KPConv (Predator_APR/models/blocks.py:235-374 with deformable=True; kpconv_deform.hip).  dkp f32
+ * [nq, 15, 3] = kernel_points + extent * offsets (blocks.py:258, 279) are the query's OWN kernel points; mod f32 [nq, 15] = 2
+ * sigmoid(offset_features[:, 45:]) (blocks.py:247) or NULL (= 1).  With diff = s[nbr[q,h]] - q - dkp[q,k], d2 = |diff|^2:
+ *   w[q,k,h]     = max(0, 1 - sqrt(d2) / extent) for a real neighbour (0 <= nbr < ns), 0 for padding   (blocks.py:326-329)
+ *   min_d2[q,k]  = min over ALL H slots of d2, a padding slot entering as the point (1e6, 1e6, 1e6)     (blocks.py:295)
+ *   num[q]       = max(1, #{h real : d2 < extent^2 for some k, and rowsum[nbr[q,h]] > 0})               (blocks.py:298-316,
+ *                  369-371: the reference's topk re-gather drops the out-of-range neighbours from the count; a support
+ *                  beyond every DEFORMED kernel point does not count, unlike apr_kpconv_weighted)
+ *   wf[q, k*cin + c] = mod[q,k] / num[q] * sum_h w[q,k,h] * x[nbr[q,h], c]                             (blocks.py:354-358)
+ * apr_kpconv_deform_weighted writes wf f32 [nq, ldwf >= 15 cin] and, when min_d2 != NULL, min_d2 f32 [nq, 15]; step 2 is the
+ * dense GEMM with the [15 cin, cout] weights, as for the rigid layer.  One wave per query on the fp32 MFMA, no atomics: the
+ * same bits on every run.
+ * Backward (num and the in-range flags are constants, as in the graph torch builds), dwf = d_out @ W^T f32 [nq, lddwf]:
+ *   apr_kpconv_deform_dfeat_contrib: contrib f32 [nq * H, cin], row (q, h) = sum_k mod w dwf[q, k*cin + :] / num for a real
+ *     neighbour; rows of padding neighbours are left untouched.  apr_reverse_gather(_range) sums them per support row.
+ *   apr_kpconv_deform_dgeom: with P[h,k] = <x[nbr[q,h], :], dwf[q, k*cin + :]> (fp32 MFMA, dwf[q] stationary),
+ *     d_mod[q,k] = sum_h w P / num,   d_dkp[q,k,:] = mod / num * sum_{h real, 0 < d < extent} diff / (d * extent) * P;
+ *     every element of d_dkp f32 [nq, 15, 3] and d_mod f32 [nq, 15] is written (mod == NULL: d_mod is still written).
+ *     DEVIATION: a neighbour exactly on a deformed kernel point (d = 0) contributes 0; the reference's graph gives NaN.
+ * All three: n_kp = 15, cin % 64 == 0, 64 <= cin <= 512, 1 <= H <= 128, 0 < ns < 2^30, extent > 0, x / wf / dwf rows 16-byte
+ * aligned where they are read or written as vectors (weighted: x, wf; dgeom: x, dwf).  Everything else returns APR_EINVAL
+ * before any launch and leaves the outputs untouched; nq == 0 launches nothing.  rowsum: apr_row_sums of x. */
+int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                               const float* x, int64_t ldx, int32_t cin, const float* dkp, const float* mod, int32_t n_kp,
+                               float extent, const float* rowsum, float* wf, int64_t ldwf, float* min_d2, void* stream);
+int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                    int32_t H, const float* dwf, int64_t lddwf, int32_t cin, const float* dkp, const float* mod,
+                                    int32_t n_kp, float extent, const float* rowsum, float* contrib, void* stream);
+int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                            const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
+                            const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
+                            void* stream);
 size_t apr_reverse_table_scratch_bytes(int64_t nq, int32_t H, int64_t ns);
 int apr_reverse_table_build(const int32_t* nbr, int64_t nq, int32_t H, int64_t ns, int32_t* rev_t, int32_t* start,
                             void* scratch, size_t scratch_bytes, void* stream);
