@@ -42,6 +42,16 @@ class SpconvDesc(C.Structure):
 # apr_spconv_route's ids (the APR_ROUTE_* enum of include/apr_hip.h)
 ROUTE_TILE, ROUTE_WS, ROUTE_WS_BF3, ROUTE_WS3, ROUTE_OS, ROUTE_DENSE_ROWS, ROUTE_DENSE_GEMM = range(7)
 
+# apr_spconv_tile_variant's ids (APR_TILE_* and APR_TILE_ID of include/apr_hip.h), apr_spconv_wgrad_plan's kernels
+TILE_NONE, TILE_PAIRS, TILE_MFMA, TILE_DENSE, TILE_BIGK, TILE_SMALLCIN, TILE_GENERIC, TILE_DENSE_BF3 = range(8)
+TILE_FLAG, TILE_NW8 = 1 << 22, 1 << 23
+WGRAD_BF3, WGRAD_PARTIAL = 1, 2
+
+
+def tile_id(kernel, tm=0, cn=0, ck=0, flag=False):
+    """APR_TILE_ID(kernel, tm, cn, ck) [| APR_TILE_FLAG]."""
+    return (kernel << 24) | (tm << 14) | (cn << 7) | ck | (TILE_FLAG if flag else 0)
+
 
 class ResunetLayer(C.Structure):
     """struct apr_resunet_layer (include/apr_hip.h)."""
@@ -134,6 +144,9 @@ PROTOTYPES = {
     "apr_spconv_wgrad": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "apr_spconv_wgrad_same_level": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "apr_spconv_route": (_i32, [_p]),
+    "apr_spconv_tile_variant": (_i32, [_p]),
+    "apr_dense_gemm_bf3_variant": (_i32, [_i64, _i32, _i32]),
+    "apr_spconv_wgrad_plan": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _i32, _p]),
     "apr_spconv_ws_supported": (_i32, [_i32, _i32, _i32]),
     "apr_spconv_bigk_supported": (_i32, [_i32, _i32, _i32]),
     "apr_spconv_fwd_batch": (C.c_int, [_p, _i32, _p]),

@@ -68,6 +68,7 @@ int apr_internal_fill(void* ptr, int32_t byte_value, size_t bytes, hipStream_t s
 
 // dense.hip: [M, cin] x [cin, cout] with the sparse conv's epilogue (identity kernel map); _ok = shape is supported
 bool apr_internal_dense_ok(int64_t M, int32_t cin, int32_t cout);
+int apr_internal_dense_g(int64_t M, int32_t cout);      // 1 / 2: k_dense_gemm<G>, 64 G rows per tile
 bool apr_internal_dense_rows_route(int64_t M, int32_t cin, int32_t cout);      // dense_rows.hip
 bool apr_internal_ws_bf3_only(const void* w_bf3, int32_t cin);                 // spconv_ws.hip
 int apr_internal_dense_gemm(const float* in, int64_t ldi, int64_t M, int32_t cin, int32_t cout, const float* wp,

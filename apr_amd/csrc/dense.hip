@@ -374,12 +374,17 @@ bool apr_internal_dense_ok(int64_t M, int32_t cin, int32_t cout) {
   return s_on && M > 0 && M < (1ll << 31) && cin % 64 == 0 && cout % 64 == 0 && cdiv64(M, 64) * (cout / 64) >= 144;
 }
 
+// 64 G rows per tile of k_dense_gemm<G>: 128-row tiles halve the weight staging per row but need enough workgroups to fill
+// 256 CUs (>= 2 per CU)
+int apr_internal_dense_g(int64_t M, int32_t cout) {
+  return cdiv64(M, 128) * (cout / 64) >= 512 ? 2 : 1;
+}
+
 int apr_internal_dense_gemm(const float* in, int64_t ldi, int64_t M, int32_t cin, int32_t cout, const float* wp,
                             const float* scale, const float* shift, const float* residual, int64_t ldr, int32_t relu,
                             float* out, int64_t ldo, hipStream_t st) {
-  // 128-row tiles halve the weight staging per row but need enough workgroups to fill 256 CUs (>= 2 per CU)
   const int64_t ncol = cout / 64;
-  const bool big = cdiv64(M, 128) * ncol >= 512;
+  const bool big = apr_internal_dense_g(M, cout) == 2;
   if (big)
     hipLaunchKernelGGL(k_dense_gemm<2>, dim3((unsigned)(cdiv64(M, 128) * ncol)), dim3(256), 0, st, in, ldi, (int)M, cin,
                        cout, wp, scale, shift, residual, ldr, relu, out, ldo);
@@ -411,6 +416,14 @@ static int dense_astg_attr() {      // 48 KB static + 16 G KB dynamic LDS: above
   return APR_OK;
 }
 
+// The instance of k_dense_gemm_bf3 that apr_dense_gemm_bf3 launches for a shape: 64- or 128-row tiles, APR_TILE_FLAG when the
+// rows go through LDS.  Host arithmetic only.
+APR_API int32_t apr_dense_gemm_bf3_variant(int64_t M, int32_t cin, int32_t cout) {
+  static const int s_g = env_int("APR_DENSE_G", 0);      // A/B switch: force 64-row (1) or 128-row (2) tiles
+  const bool g2 = s_g == 2 || (s_g == 0 && apr_internal_dense_g(M, cout) == 2);
+  return APR_TILE_ID(APR_TILE_DENSE_BF3, g2 ? 128 : 64, 64, 64) | (dense_astg(cin) ? APR_TILE_FLAG : 0);
+}
+
 // The same contraction on the bf16 3-way split (k_dense_gemm_bf3): out = act((in @ W) * scale + shift + residual) for
 // an identity map.  w_bf3: apr_spconv_pack_weights_bf3(w, K = 1, cin, cout).  cin % 64 == 0, cout % 64 == 0, rows of
 // in / out / residual 16-B aligned (ld % 4 == 0).
@@ -429,9 +442,9 @@ APR_API int apr_dense_gemm_bf3(const float* in, int64_t ldi, int64_t M, int32_t 
                 "apr_dense_gemm_bf3: scale / shift must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int64_t ncol = cout / 64;
-  static const int s_g = env_int("APR_DENSE_G", 0);      // A/B switch: force 64-row (1) or 128-row (2) tiles
-  const bool g2 = s_g == 2 || (s_g == 0 && cdiv64(M, 128) * ncol >= 512);
-  const bool astg = dense_astg(cin);
+  const int32_t id = apr_dense_gemm_bf3_variant(M, cin, cout);
+  const bool g2 = APR_TILE_TM(id) == 128;
+  const bool astg = (id & APR_TILE_FLAG) != 0;
   if (astg) {
     int rca = dense_astg_attr();
     if (rca != APR_OK) return rca;

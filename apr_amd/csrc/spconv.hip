@@ -561,7 +561,11 @@ APR_API int apr_weights_flip_transpose(const float* w, int32_t K, int32_t cin, i
   return APR_OK;
 }
 
-static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, bool* fused) {
+// Which kernel and which template instance the tile family runs a descriptor on (APR_TILE_ID of include/apr_hip.h): host
+// arithmetic on the shape, the leading dimensions and the pointers' alignment, no HIP call.  spconv_fwd_plain switches on the
+// id and on nothing else.  `l2f`: the caller wants the rows normalised; the id carries APR_TILE_FLAG when the pairs kernel does
+// that in its own epilogue.  0 = nothing to launch (no rows); < 0: APR_EINVAL, apr_last_error() says why.
+static int32_t tile_variant(const apr_spconv_desc& d, int l2f) {
   const int64_t n_out = d.n_out;
   const int K = d.K, cin = d.cin, cout = d.cout;
   APR_CHECK_ARG(n_out >= 0 && n_out < (1ll << 31), "apr_spconv_fwd: n_out=%lld", (long long)n_out);
@@ -569,7 +573,7 @@ static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, b
   APR_CHECK_ARG(d.nbr != nullptr || K == 1, "apr_spconv_fwd: identity map needs K == 1");
   APR_CHECK_ARG(d.ldi >= cin && d.ldo >= cout, "apr_spconv_fwd: leading dimension smaller than channels");
   APR_CHECK_ARG(!d.residual || d.ldr >= cout, "apr_spconv_fwd: ldr < cout");
-  if (n_out == 0) return APR_OK;
+  if (n_out == 0) return APR_TILE_NONE;
   static const int s_impl = env_int("APR_SPCONV_IMPL", 2);      // 1 = dense-tile kernel, 2 = pair-compacted
   static const int s_tm = env_int("APR_SPCONV_TM", 0);           // 0 = heuristic
   const bool vec_ok = (d.ldi % 4) == 0 && (((uintptr_t)d.in) & 15) == 0 && (d.ldo % 4) == 0 &&
@@ -578,79 +582,95 @@ static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, b
   // identity map (dense layer: K = 1 convolutions, Predator's Linear layers and KPConv's second step): dense.hip
   if (d.nbr == nullptr && K == 1 && vec_ok && apr_internal_dense_ok(n_out, cin, cout) &&
       ((((uintptr_t)d.scale) | ((uintptr_t)d.shift) | ((uintptr_t)d.w_packed)) & 15) == 0)
-    return apr_internal_dense_gemm(d.in, d.ldi, n_out, cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu,
-                                   d.out, d.ldo, st);
+    return APR_TILE_ID(APR_TILE_DENSE, 64 * apr_internal_dense_g(n_out, cout), 64, 64);
   if (s_impl == 2 && use_mfma(K, cin, cout) && K <= kKMax && vec_ok) {
-    // the row normalisation rides in this kernel's epilogue when a tile holds the whole row (CN == cout)
-    const int l2k = (l2f && (cout == 32 || cout == 64)) ? 1 : 0;
     static const int s_nw = env_int("APR_SPCONV_NW", 4);
-    if (l2k && !(s_nw == 8 && cout % 64 == 0) && !(cout == 64 && env_int("APR_SPCONV_CN", 0) == 32)) *fused = true;
-#define APR_PAIRS(TM_, CN_, CK_) return launch_pairs<TM_, CN_, CK_, 4>(d, st, *fused ? 1 : 0)
     if (s_nw == 8 && cout % 64 == 0)   // 8-wave tiles: 32-row tile, 32-channel pieces (<= 128 VGPRs, 4 waves/SIMD)
-      return launch_pairs<32, 64, 32, 8>(d, st);
+      return APR_TILE_ID(APR_TILE_PAIRS, 32, 64, 32) | APR_TILE_NW8;
     static const int s_ck = env_int("APR_SPCONV_CK", 0);
     static const int s_cn = env_int("APR_SPCONV_CN", 0);
     const bool cn64 = (cout % 64 == 0) && s_cn != 32;
     const bool ck64 = (cin % 64 == 0) && s_ck != 32;
+    // the row normalisation rides in this kernel's epilogue when a tile holds the whole row (CN == cout)
+    const bool fused = l2f && (cout == 32 || cout == 64) && !(cout == 64 && s_cn == 32);
     // 64-row tiles halve the weight re-reads but need >= ~400 workgroups to fill 256 CUs; below that 32-row
     // tiles win.  16-row tiles / 32-channel slices (APR_SPCONV_TM=16, APR_SPCONV_CN=32) measured slower on
     // every layer of the encoder: the deep layers are bound by the weight stream, not by parallelism — they
     // go through the weight-stationary path (spconv_ws.hip) instead.
     int tm = s_tm;
     if (!tm) tm = cdiv64(n_out, 64) * (cout / (cn64 ? 64 : 32)) >= 400 ? 64 : 32;
-    if (tm == 64) {
-      if (cn64 && ck64) APR_PAIRS(64, 64, 64);
-      if (cn64) APR_PAIRS(64, 64, 32);
-      if (ck64) APR_PAIRS(64, 32, 64);
-      APR_PAIRS(64, 32, 32);
-    }
-    if (tm == 16) {
-      if (cn64 && ck64) APR_PAIRS(16, 64, 64);
-      if (cn64) APR_PAIRS(16, 64, 32);
-      if (ck64) APR_PAIRS(16, 32, 64);
-      APR_PAIRS(16, 32, 32);
-    }
-    if (cn64 && ck64) APR_PAIRS(32, 64, 64);
-    if (cn64) APR_PAIRS(32, 64, 32);
-    if (ck64) APR_PAIRS(32, 32, 64);
-    APR_PAIRS(32, 32, 32);
-#undef APR_PAIRS
+    if (tm != 64 && tm != 16) tm = 32;
+    return APR_TILE_ID(APR_TILE_PAIRS, tm, cn64 ? 64 : 32, ck64 ? 64 : 32) | (fused ? APR_TILE_FLAG : 0);
   }
-  if (use_mfma(K, cin, cout) && (d.ldi % 4) == 0 && (((uintptr_t)d.in) & 15) == 0) {
-#define APR_MFMA(CN_, WM_, WN_, CK_) \
-  return big ? launch_mfma<64, CN_, WM_, WN_, CK_>(d, st) : launch_mfma<32, CN_, WM_, WN_, CK_>(d, st)
-    const bool big = n_out >= 32768, cn64 = cout % 64 == 0, ck64 = cin % 64 == 0;
-    if (cn64 && ck64) APR_MFMA(64, 1, 4, 64);
-    if (cn64) APR_MFMA(64, 1, 4, 32);
-    if (ck64) APR_MFMA(32, 2, 2, 64);
-    APR_MFMA(32, 2, 2, 32);
-#undef APR_MFMA
-  }
+  if (use_mfma(K, cin, cout) && (d.ldi % 4) == 0 && (((uintptr_t)d.in) & 15) == 0)
+    return APR_TILE_ID(APR_TILE_MFMA, n_out >= 32768 ? 64 : 32, cout % 64 == 0 ? 64 : 32, cin % 64 == 0 ? 64 : 32);
   APR_CHECK_ARG(!use_mfma(K, cin, cout),
                 "apr_spconv_fwd: MFMA-shaped layer needs 16-B aligned input rows (ldi %% 4 == 0)");
   // 32 < K <= 125 with real channel counts (the symmetric recipe's 5^3 generator conv1 and its input gradient): the
   // pair-compacted MFMA kernel of spconv_bigk.hip on the same plain [K, cin, cout] buffer; APR_SPCONV_BIGK=0: generic
   static const int s_bigk = env_int("APR_SPCONV_BIGK", 1);
   if (s_bigk && apr_spconv_bigk_supported(K, cin, cout) && apr_internal_spconv_bigk_aligned(d))
-    return apr_internal_spconv_bigk(d, st);
+    return APR_TILE_ID(APR_TILE_BIGK, 0, 0, 0);
   if (d.nbr && (cin == 1 || cin == 3) && cout % 32 == 0 && (size_t)64 * K * 4 <= 64 * 1024 &&
-      (((uintptr_t)d.w_packed) & 15) == 0) {
-    const unsigned grid = (unsigned)cdiv64(n_out, 64);
-    const size_t lds = (size_t)64 * K * 4;
-    if (cin == 1)
-      hipLaunchKernelGGL(k_spconv_smallcin<1>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
-                         d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
-    else
-      hipLaunchKernelGGL(k_spconv_smallcin<3>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
-                         d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
-    APR_LAUNCH_CHECK();
-    return APR_OK;
+      (((uintptr_t)d.w_packed) & 15) == 0)
+    return APR_TILE_ID(APR_TILE_SMALLCIN, 64, 0, cin);
+  return APR_TILE_ID(APR_TILE_GENERIC, 0, 0, 0);
+}
+
+APR_API int32_t apr_spconv_tile_variant(const apr_spconv_desc* dp) {
+  APR_CHECK_ARG(dp != nullptr, "apr_spconv_tile_variant: null descriptor");
+  return tile_variant(*dp, dp->l2norm);
+}
+
+static int spconv_fwd_plain(const apr_spconv_desc& d, hipStream_t st, int l2f, bool* fused) {
+  const int32_t id = tile_variant(d, l2f);
+  if (id < 0) return id;
+  if (id == APR_TILE_NONE) return APR_OK;
+  const int64_t n_out = d.n_out;
+  const int K = d.K, cin = d.cin, cout = d.cout;
+  *fused = APR_TILE_KERNEL(id) == APR_TILE_PAIRS && (id & APR_TILE_FLAG) != 0;
+  const int l2k = *fused ? 1 : 0;
+  switch (id & ~APR_TILE_FLAG) {
+    case APR_TILE_ID(APR_TILE_DENSE, 64, 64, 64):
+    case APR_TILE_ID(APR_TILE_DENSE, 128, 64, 64):
+      return apr_internal_dense_gemm(d.in, d.ldi, n_out, cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu,
+                                     d.out, d.ldo, st);
+    case APR_TILE_ID(APR_TILE_PAIRS, 32, 64, 32) | APR_TILE_NW8: return launch_pairs<32, 64, 32, 8>(d, st);
+#define APR_PAIRS(TM_, CN_, CK_) \
+  case APR_TILE_ID(APR_TILE_PAIRS, TM_, CN_, CK_): return launch_pairs<TM_, CN_, CK_, 4>(d, st, l2k)
+    APR_PAIRS(64, 64, 64); APR_PAIRS(64, 64, 32); APR_PAIRS(64, 32, 64); APR_PAIRS(64, 32, 32);
+    APR_PAIRS(16, 64, 64); APR_PAIRS(16, 64, 32); APR_PAIRS(16, 32, 64); APR_PAIRS(16, 32, 32);
+    APR_PAIRS(32, 64, 64); APR_PAIRS(32, 64, 32); APR_PAIRS(32, 32, 64); APR_PAIRS(32, 32, 32);
+#undef APR_PAIRS
+#define APR_MFMA(TM_, CN_, WM_, WN_, CK_) \
+  case APR_TILE_ID(APR_TILE_MFMA, TM_, CN_, CK_): return launch_mfma<TM_, CN_, WM_, WN_, CK_>(d, st)
+    APR_MFMA(64, 64, 1, 4, 64); APR_MFMA(64, 64, 1, 4, 32); APR_MFMA(64, 32, 2, 2, 64); APR_MFMA(64, 32, 2, 2, 32);
+    APR_MFMA(32, 64, 1, 4, 64); APR_MFMA(32, 64, 1, 4, 32); APR_MFMA(32, 32, 2, 2, 64); APR_MFMA(32, 32, 2, 2, 32);
+#undef APR_MFMA
+    case APR_TILE_ID(APR_TILE_BIGK, 0, 0, 0): return apr_internal_spconv_bigk(d, st);
+    case APR_TILE_ID(APR_TILE_SMALLCIN, 64, 0, 1):
+    case APR_TILE_ID(APR_TILE_SMALLCIN, 64, 0, 3): {
+      const unsigned grid = (unsigned)cdiv64(n_out, 64);
+      const size_t lds = (size_t)64 * K * 4;
+      if (cin == 1)
+        hipLaunchKernelGGL(k_spconv_smallcin<1>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
+                           d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
+      else
+        hipLaunchKernelGGL(k_spconv_smallcin<3>, dim3(grid), dim3(256), lds, st, d.in, d.ldi, d.nbr, (int)n_out, K, cout,
+                           d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
+      APR_LAUNCH_CHECK();
+      return APR_OK;
+    }
+    case APR_TILE_ID(APR_TILE_GENERIC, 0, 0, 0): {
+      int64_t total = n_out * cout;
+      hipLaunchKernelGGL(k_spconv_generic, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, d.in, d.ldi, d.nbr, n_out, K,
+                         cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
+      APR_LAUNCH_CHECK();
+      return APR_OK;
+    }
   }
-  int64_t total = n_out * cout;
-  hipLaunchKernelGGL(k_spconv_generic, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, d.in, d.ldi, d.nbr, n_out, K,
-                     cin, cout, d.w_packed, d.scale, d.shift, d.residual, d.ldr, d.relu, d.out, d.ldo);
-  APR_LAUNCH_CHECK();
-  return APR_OK;
+  apr_set_error("apr_spconv_fwd: no kernel instance for tile variant 0x%x", (unsigned)id);
+  return APR_EINVAL;
 }
 
 // apr_spconv_fwd + optional row normalisation of the result (out[j] /= |out[j]|_2): fused into the tile kernel's

@@ -349,6 +349,25 @@ static int launch_wgrad_bf3(const float* in, int64_t ldi, const float* dout, int
   return APR_OK;
 }
 
+// What apr_spconv_wgrad[_same_level] launches for these operands: plan = {kernel, CI, CO, S_all, S_c, k_c}.  APR_WGRAD_BF3:
+// k_wgrad_bf3<CI, CO> over S_all splits per offset (S_c for the centre offset k_c of a same-level map, k_c = -1 otherwise) and
+// k_wgrad_reduce_work; APR_WGRAD_PARTIAL (rows of x / dout not 16-byte aligned, widths off the 32-channel granule): the fp32
+// k_wgrad_partial over 512-row chunks and k_wgrad_reduce, with S_all = S_c = the chunk count.  Host arithmetic only.
+APR_API int apr_spconv_wgrad_plan(const float* in, int64_t ldi, const float* dout, int64_t ldo, int64_t n_out, int32_t K,
+                                  int32_t cin, int32_t cout, int32_t same_level, int32_t* plan) {
+  APR_CHECK_ARG(plan != nullptr && n_out > 0 && K >= 1 && cin >= 1 && cout >= 1, "apr_spconv_wgrad_plan: bad arguments");
+  if (wgrad_bf3_ok(cin, cout) && ldi % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)dout & 15) == 0) {
+    int CI, CO, S_all, S_c, k_c;
+    wgrad_splits(n_out, K, cin, cout, same_level, CI, CO, S_all, S_c, k_c);
+    plan[0] = APR_WGRAD_BF3; plan[1] = CI; plan[2] = CO; plan[3] = S_all; plan[4] = S_c; plan[5] = k_c;
+    return APR_OK;
+  }
+  const int64_t nchunk = cdiv64(n_out, kChunkRows);
+  APR_CHECK_ARG(nchunk < 65536 * 32 && K <= 65535, "apr_spconv_wgrad: too many rows / offsets for one launch");
+  plan[0] = APR_WGRAD_PARTIAL; plan[1] = 64; plan[2] = 64; plan[3] = plan[4] = (int32_t)nchunk; plan[5] = -1;
+  return APR_OK;
+}
+
 static int spconv_wgrad_impl(const float* in, int64_t ldi, const float* dout, int64_t ldo, const int32_t* nbr,
                              int64_t n_out, int32_t K, int32_t cin, int32_t cout, int same_level, float* dw, void* scratch,
                              size_t scratch_bytes, void* stream) {
@@ -358,9 +377,11 @@ static int spconv_wgrad_impl(const float* in, int64_t ldi, const float* dout, in
   APR_CHECK_ARG(scratch_bytes >= apr_spconv_wgrad_scratch_bytes(n_out, K, cin, cout), "apr_spconv_wgrad: scratch too small");
   float* part = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
   const int64_t per_chunk = (int64_t)K * cin * cout;
-  if (wgrad_bf3_ok(cin, cout) && ldi % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)dout & 15) == 0) {
-    int CI, CO, S_all, S_c, k_c;
-    wgrad_splits(n_out, K, cin, cout, same_level, CI, CO, S_all, S_c, k_c);
+  int32_t plan[6];
+  int rcp = apr_spconv_wgrad_plan(in, ldi, dout, ldo, n_out, K, cin, cout, same_level, plan);
+  if (rcp != APR_OK) return rcp;
+  if (plan[0] == APR_WGRAD_BF3) {
+    const int CI = plan[1], CO = plan[2], S_all = plan[3], S_c = plan[4], k_c = plan[5];
     int rc;
 #define WG_CASE(A, B) \
   if (CI == A && CO == B) rc = launch_wgrad_bf3<A, B>(in, ldi, dout, ldo, nbr, n_out, K, cin, cout, S_all, S_c, k_c, part, st); else
@@ -372,8 +393,7 @@ static int spconv_wgrad_impl(const float* in, int64_t ldi, const float* dout, in
     APR_LAUNCH_CHECK();
     return APR_OK;
   }
-  const int64_t nchunk = cdiv64(n_out, kChunkRows);
-  APR_CHECK_ARG(nchunk < 65536 * 32 && K <= 65535, "apr_spconv_wgrad: too many rows / offsets for one launch");
+  const int64_t nchunk = plan[3];
   APR_CHECK_ARG(scratch_bytes >= (size_t)nchunk * K * cin * cout * 4 + 256, "apr_spconv_wgrad: scratch too small");
   const unsigned nz = (unsigned)(((cin + 63) / 64) * ((cout + 63) / 64));
   hipLaunchKernelGGL(k_wgrad_partial, dim3((unsigned)nchunk, (unsigned)K, nz), dim3(256), 0, st, in, ldi, dout, ldo,

@@ -298,6 +298,14 @@ int apr_spconv_wgrad(const float* in, int64_t ldi, const float* dout, int64_t ld
 int apr_spconv_wgrad_same_level(const float* in, int64_t ldi, const float* dout, int64_t ldo, const int32_t* nbr,
                                 int64_t n_out, int32_t K, int32_t cin, int32_t cout, float* dw, void* scratch,
                                 size_t scratch_bytes, void* stream);
+/* What the two entry points launch for these operands (host only, no HIP call; the launcher follows it):
+ * plan[6] = {kernel, CI, CO, S_all, S_c, k_c}.  APR_WGRAD_BF3: k_wgrad_bf3<CI, CO> on the bf16 split, S_all splits of the
+ * 512-row blocks per offset, S_c for the centre offset k_c of a same-level map (k_c = -1: no such offset).
+ * APR_WGRAD_PARTIAL: the fp32 k_wgrad_partial (rows of in / dout not 16-byte aligned, or a width off the 32-channel
+ * granule): CI = CO = 64, S_all = S_c = the number of 512-row chunks, k_c = -1.  in / dout are looked at for alignment only. */
+enum { APR_WGRAD_BF3 = 1, APR_WGRAD_PARTIAL = 2 };
+int apr_spconv_wgrad_plan(const float* in, int64_t ldi, const float* dout, int64_t ldo, int64_t n_out, int32_t K,
+                          int32_t cin, int32_t cout, int32_t same_level, int32_t* plan);
 
 /* Triple pair lists for 27-offset maps (spconv_ws.hip): offsets are x fastest, so k = 3t + j are the three x-neighbours of
  * one (dy, dz); an ENTRY of triple t is an output row with its up to three input rows, and the gemm writes ONE product
@@ -360,6 +368,29 @@ int32_t apr_spconv_ws_supported(int32_t K, int32_t cin, int32_t cout);
  * generator conv1, FCGF_APR/lib/complement_trainer.py:52-60, and its input gradient).  Reads the plain [K, cin, cout]
  * buffer that apr_spconv_pack_weights leaves for K > 32. */
 int32_t apr_spconv_bigk_supported(int32_t K, int32_t cin, int32_t cout);
+/* Inside APR_ROUTE_TILE: the kernel and template instance that apr_spconv_fwd launches for a descriptor (d->l2norm says
+ * whether the rows are to be normalised).  Host only, no HIP call; the launcher switches on this id and on nothing else.
+ * id = APR_TILE_ID(kernel, TM, CN, CK) [| APR_TILE_FLAG] [| APR_TILE_NW8]:
+ *   APR_TILE_PAIRS     k_spconv_pairs<TM, CN, CK, 4>; FLAG: the row normalisation rides in its epilogue; NW8: the 8-wave form
+ *   APR_TILE_MFMA      k_spconv_mfma<TM, CN, .., CK> (out / residual rows not 16-byte aligned, or K 28..32)
+ *   APR_TILE_DENSE     k_dense_gemm<TM / 64> (identity map, K = 1, enough workgroups); CN = CK = 64
+ *   APR_TILE_BIGK      spconv_bigk.hip (32 < K <= 125 over real channels)
+ *   APR_TILE_SMALLCIN  k_spconv_smallcin<CK> (cin 1 / 3): TM = 64 rows per workgroup, CN = 0
+ *   APR_TILE_GENERIC   k_spconv_generic
+ * APR_TILE_NONE (0): no rows, nothing is launched.  < 0: APR_EINVAL (a bad shape; an MFMA-shaped layer whose INPUT rows are
+ * not 16-byte aligned), apr_last_error() says why.  apr_dense_gemm_bf3_variant: the same for apr_dense_gemm_bf3, kernel
+ * APR_TILE_DENSE_BF3, TM 64 / 128, FLAG: the rows are staged through LDS (cin >= 128). */
+enum { APR_TILE_NONE = 0, APR_TILE_PAIRS, APR_TILE_MFMA, APR_TILE_DENSE, APR_TILE_BIGK, APR_TILE_SMALLCIN, APR_TILE_GENERIC,
+       APR_TILE_DENSE_BF3 };
+#define APR_TILE_ID(kernel, tm, cn, ck) (((kernel) << 24) | ((tm) << 14) | ((cn) << 7) | (ck))
+#define APR_TILE_FLAG (1 << 22)
+#define APR_TILE_NW8 (1 << 23)
+#define APR_TILE_KERNEL(id) ((id) >> 24)
+#define APR_TILE_TM(id) (((id) >> 14) & 255)
+#define APR_TILE_CN(id) (((id) >> 7) & 127)
+#define APR_TILE_CK(id) ((id) & 127)
+int32_t apr_spconv_tile_variant(const apr_spconv_desc* d);
+int32_t apr_dense_gemm_bf3_variant(int64_t M, int32_t cin, int32_t cout);
 int apr_spconv_fwd_batch(const apr_spconv_desc* descs_host, int32_t n, void* stream);
 /* Same, with one HIP event pair per launch recorded on `stream` (around the conv kernels only, not a pair-list
  * build); synchronises and returns each layer's elapsed milliseconds in layer_ms[n].  Measurement aid
