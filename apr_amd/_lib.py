@@ -238,6 +238,17 @@ PROTOTYPES = {
     "apr_kpconv_deform_dfeat_contrib": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p, _p]),
     "apr_kpconv_deform_dgeom": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i32, _f32, _p, _p, _p,
                                           _p]),
+    # the five above + (influence, closest) before the stream
+    "apr_kpconv_weighted_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _i32, _i32,
+                                           _p]),
+    "apr_kpconv_dfeat_contrib_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i32, _i32,
+                                                _p]),
+    "apr_kpconv_deform_weighted_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p, _i64,
+                                                  _p, _i32, _i32, _p]),
+    "apr_kpconv_deform_dfeat_contrib_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p,
+                                                       _i32, _i32, _p]),
+    "apr_kpconv_deform_dgeom_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i32, _f32, _p, _p,
+                                               _p, _i32, _i32, _p]),
     "apr_reverse_table_scratch_bytes": (_sz, [_i64, _i32, _i64]),
     "apr_reverse_table_build": (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p, _sz, _p]),
     "apr_reverse_gather": (C.c_int, [_p, _i32, _p, _p, _i64, _p, _i64, _p]),

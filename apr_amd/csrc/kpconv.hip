@@ -11,7 +11,11 @@
 // divided by the neighbour count.  Step 2 is the dense [Nq, 15*Cin] x [15*Cin, Cout] GEMM on the
 // sparse-conv MFMA kernel (identity map).  The remaining kernels are the small gather / reduce
 // ops of the blocks and of the overlap-attention module; none materialises an N x N tensor.
+// The other influence functions (constant, gaussian) and the `closest` aggregation (blocks.py:61-68, 320-345) are
+// compile-time parameters of the correlation kernels and of the deterministic feature gradient (kpconv_modes.h); the
+// <kLinear, false> instantiations are the kernels described above, instruction for instruction.
 #include "common.h"
+#include "kpconv_modes.h"
 
 namespace {
 
@@ -29,6 +33,11 @@ __global__ void k_row_sums(const float* __restrict__ x, int64_t ld, int64_t n, i
   if (lane == 0) out[row] = s;
 }
 
+__device__ inline float kp_d2(float dx, float dy, float dz, float kx, float ky, float kz) {
+  const float ex = dx - kx, ey = dy - ky, ez = dz - kz;
+  return ex * ex + ey * ey + ez * ez;
+}
+
 __device__ inline float kp_weight(float dx, float dy, float dz, float kx, float ky, float kz, float inv_extent) {
   const float ex = dx - kx, ey = dy - ky, ez = dz - kz;
   const float d2 = ex * ex + ey * ey + ez * ez;
@@ -36,13 +45,17 @@ __device__ inline float kp_weight(float dx, float dy, float dz, float kx, float 
 }
 
 // Step 1, MFMA form.  One wave per query; Cin % 64 == 0; NG = 64-channel groups per pass.
-template <int NG>
+// INF / CLOSEST: the influence function and the aggregation (blocks.py:320-345) as compile-time parameters; <.., kLinear,
+// false> is the kernel as it was.  With CLOSEST the lane that stages slot h -- it holds the centred point -- records the
+// neighbour's closest kernel point (kpmode::closest_kp), and the A operand of every other kernel point is 0.
+template <int NG, int INF = kpmode::kLinear, bool CLOSEST = false>
 __global__ __launch_bounds__(256) void k_kpconv_weighted_mfma(
     const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
     const float* __restrict__ x, int64_t ldx, int cin, const float* __restrict__ kp, float extent,
     const float* __restrict__ rowsum, float* __restrict__ wf, int64_t ldwf, int nq, int ns, int xcd_swz) {
   __shared__ int s_idx[4][kMaxH];
   __shared__ float s_diff[4][kMaxH][3];
+  __shared__ unsigned char s_cl[CLOSEST ? 4 : 1][CLOSEST ? kMaxH : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, qd = lane >> 4;
   int blk = blockIdx.x;
@@ -70,10 +83,12 @@ __global__ __launch_bounds__(256) void k_kpconv_weighted_mfma(
     }
     s_idx[wave][h] = idx;
     s_diff[wave][h][0] = dx; s_diff[wave][h][1] = dy; s_diff[wave][h][2] = dz;
+    if constexpr (CLOSEST) s_cl[wave][h] = idx >= 0 ? (unsigned char)kpmode::closest_kp(dx, dy, dz, kp, 0.f) : 0;
   }
   for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
   const float inv_num = 1.f / (float)max(cnt, 1);
   const float inv_extent = 1.f / extent;
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   const bool kvalid = r16 < kKP;
   const float kx = kvalid ? kp[3 * r16] : 0.f, ky = kvalid ? kp[3 * r16 + 1] : 0.f, kz = kvalid ? kp[3 * r16 + 2] : 0.f;
   const int nsteps = (H + 3) >> 2;
@@ -87,8 +102,15 @@ __global__ __launch_bounds__(256) void k_kpconv_weighted_mfma(
       const int h = st * 4 + qd;
       const int idx = s_idx[wave][h];
       float w = 0.f;
-      if (kvalid && idx >= 0)
-        w = kp_weight(s_diff[wave][h][0], s_diff[wave][h][1], s_diff[wave][h][2], kx, ky, kz, inv_extent);
+      if (kvalid && idx >= 0) {
+        if constexpr (INF == kpmode::kLinear)
+          w = kp_weight(s_diff[wave][h][0], s_diff[wave][h][1], s_diff[wave][h][2], kx, ky, kz, inv_extent);
+        else if constexpr (INF == kpmode::kGaussian)
+          w = kpmode::influence<INF>(kp_d2(s_diff[wave][h][0], s_diff[wave][h][1], s_diff[wave][h][2], kx, ky, kz), inv_extent, gden);
+        else
+          w = 1.f;
+        if constexpr (CLOSEST) w = (int)s_cl[wave][h] == r16 ? w : 0.f;
+      }
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         f32x4 b = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -114,7 +136,9 @@ __global__ __launch_bounds__(256) void k_kpconv_weighted_mfma(
   }
 }
 
-// Step 1, VALU form for any Cin (the first layer has Cin = 1).  One thread per (query, kernel point).
+// Step 1, VALU form for any Cin (the first layer has Cin = 1).  One thread per (query, kernel point).  With CLOSEST every
+// thread finds the neighbour's closest kernel point itself (the one statement of it, kpmode::closest_kp).
+template <int INF = kpmode::kLinear, bool CLOSEST = false>
 __global__ void k_kpconv_weighted_generic(const float* __restrict__ q_pts, const float* __restrict__ s_pts,
                                           const int* __restrict__ nbr, int H, const float* __restrict__ x, int64_t ldx,
                                           int cin, const float* __restrict__ kp, float extent,
@@ -132,14 +156,24 @@ __global__ void k_kpconv_weighted_generic(const float* __restrict__ q_pts, const
     if (idx >= 0 && idx < ns && rowsum[idx] > 0.f) ++cnt;
   }
   const float inv_num = 1.f / (float)max(cnt, 1);
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   for (int c0 = 0; c0 < cin; c0 += 8) {
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int nc = min(8, cin - c0);
     for (int h = 0; h < H; ++h) {
       const int idx = nbr[(int64_t)qi * H + h];
       if (idx < 0 || idx >= ns) continue;
-      const float w = kp_weight(s_pts[3 * (int64_t)idx] - qx, s_pts[3 * (int64_t)idx + 1] - qy,
-                                s_pts[3 * (int64_t)idx + 2] - qz, kx, ky, kz, inv_extent);
+      float w;
+      if constexpr (INF == kpmode::kLinear && !CLOSEST) {
+        w = kp_weight(s_pts[3 * (int64_t)idx] - qx, s_pts[3 * (int64_t)idx + 1] - qy,
+                      s_pts[3 * (int64_t)idx + 2] - qz, kx, ky, kz, inv_extent);
+      } else {
+        const float dx = s_pts[3 * (int64_t)idx] - qx, dy = s_pts[3 * (int64_t)idx + 1] - qy,
+                    dz = s_pts[3 * (int64_t)idx + 2] - qz;
+        w = INF == kpmode::kLinear ? kp_weight(dx, dy, dz, kx, ky, kz, inv_extent)
+                                   : kpmode::influence<INF>(kp_d2(dx, dy, dz, kx, ky, kz), inv_extent, gden);
+        if constexpr (CLOSEST) w = (kpmode::closest_kp(dx, dy, dz, kp, 0.f) & 15) == k ? w : 0.f;
+      }
       if (w == 0.f) continue;
       for (int c = 0; c < nc; ++c) acc[c] = fmaf(w, x[(int64_t)idx * ldx + c0 + c], acc[c]);
     }
@@ -154,7 +188,9 @@ __global__ void k_kpconv_weighted_generic(const float* __restrict__ q_pts, const
 // One wave per query: the 15 x H influences go to LDS once, a lane keeps the 15 values dwf[q, :, c] of its channel
 // in registers and walks the neighbours; the sums leave through float atomics (a support point is the neighbour of
 // ~H queries: the transposed table is not available, and torch's own index backward adds atomically as well).
-template <int CPL>   // channels per lane: cin <= 64 * CPL
+// INF / CLOSEST as in k_kpconv_weighted_mfma; the modes other than <kLinear, false> exist in the deterministic `contrib`
+// form only (the host launches nothing else).
+template <int CPL, int INF = kpmode::kLinear, bool CLOSEST = false>   // channels per lane: cin <= 64 * CPL
 __global__ __launch_bounds__(256) void k_kpconv_dfeat(
     const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
     const float* __restrict__ dwf, int64_t lddwf, int cin, const float* __restrict__ kp, float extent,
@@ -167,6 +203,7 @@ __global__ __launch_bounds__(256) void k_kpconv_dfeat(
   if (qi >= nq) return;
   const float qx = q_pts[3 * (int64_t)qi], qy = q_pts[3 * (int64_t)qi + 1], qz = q_pts[3 * (int64_t)qi + 2];
   const float inv_extent = 1.f / extent;
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   int cnt = 0;
   for (int h = lane; h < H; h += 64) {
     int idx = nbr[(int64_t)qi * H + h];
@@ -176,9 +213,20 @@ __global__ __launch_bounds__(256) void k_kpconv_dfeat(
       cnt += rowsum[idx] > 0.f ? 1 : 0;
       const float dx_ = s_pts[3 * (int64_t)idx] - qx, dy_ = s_pts[3 * (int64_t)idx + 1] - qy,
                   dz_ = s_pts[3 * (int64_t)idx + 2] - qz;
+      if constexpr (INF == kpmode::kLinear && !CLOSEST) {
 #pragma unroll
-      for (int k = 0; k < kKP; ++k)
-        s_w[wave][h][k] = kp_weight(dx_, dy_, dz_, kp[3 * k], kp[3 * k + 1], kp[3 * k + 2], inv_extent);
+        for (int k = 0; k < kKP; ++k)
+          s_w[wave][h][k] = kp_weight(dx_, dy_, dz_, kp[3 * k], kp[3 * k + 1], kp[3 * k + 2], inv_extent);
+      } else {
+        const int cl = CLOSEST ? (kpmode::closest_kp(dx_, dy_, dz_, kp, 0.f) & 15) : -1;
+#pragma unroll
+        for (int k = 0; k < kKP; ++k) {
+          const float w = INF == kpmode::kLinear
+                              ? kp_weight(dx_, dy_, dz_, kp[3 * k], kp[3 * k + 1], kp[3 * k + 2], inv_extent)
+                              : kpmode::influence<INF>(kp_d2(dx_, dy_, dz_, kp[3 * k], kp[3 * k + 1], kp[3 * k + 2]), inv_extent, gden);
+          s_w[wave][h][k] = (!CLOSEST || k == cl) ? w : 0.f;
+        }
+      }
     }
   }
   for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
@@ -837,9 +885,17 @@ APR_API int apr_row_sums(const float* x, int64_t ld, int64_t n, int32_t c, float
   return APR_OK;
 }
 
-APR_API int apr_kpconv_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
-                                int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
-                                int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream) {
+static int kpconv_xcd() {
+  static const int s_xcd = env_int("APR_KPCONV_XCD", 1);      // A/B switch
+  return s_xcd;
+}
+
+// One body for apr_kpconv_weighted (INF = kLinear, CLOSEST = false: the launches it always made) and the other five
+// modes of apr_kpconv_weighted_mode.
+template <int INF, bool CLOSEST>
+static int kpconv_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                           const float* x, int64_t ldx, int32_t cin, const float* kernel_points, int32_t n_kp,
+                           float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_CHECK_ARG(n_kp == kKP, "apr_kpconv_weighted: built for %d kernel points, got %d", kKP, n_kp);
   APR_CHECK_ARG(nq >= 0 && ns > 0 && H > 0 && cin > 0 && extent > 0.f, "apr_kpconv_weighted: bad arguments");
@@ -848,24 +904,45 @@ APR_API int apr_kpconv_weighted(const float* q_pts, int64_t nq, const float* s_p
   const bool vec = cin % 64 == 0 && H <= kMaxH && ldx % 4 == 0 && ldwf % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)wf)) & 15) == 0;
   if (vec) {
     const unsigned grid = (unsigned)cdiv64(nq, 4);
-    static const int s_xcd = env_int("APR_KPCONV_XCD", 1);      // A/B switch
+    const int s_xcd = kpconv_xcd();
     if (cin >= 256)
-      hipLaunchKernelGGL(k_kpconv_weighted_mfma<4>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, cin,
-                         kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
+      hipLaunchKernelGGL((k_kpconv_weighted_mfma<4, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx,
+                         cin, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
     else if (cin == 128)
-      hipLaunchKernelGGL(k_kpconv_weighted_mfma<2>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, cin,
-                         kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
+      hipLaunchKernelGGL((k_kpconv_weighted_mfma<2, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx,
+                         cin, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
     else
-      hipLaunchKernelGGL(k_kpconv_weighted_mfma<1>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, cin,
-                         kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
+      hipLaunchKernelGGL((k_kpconv_weighted_mfma<1, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx,
+                         cin, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, s_xcd);
   } else {
-    hipLaunchKernelGGL(k_kpconv_weighted_generic, dim3((unsigned)cdiv64(nq * kKP, 256)), dim3(256), 0, st, q_pts, s_pts,
-                       nbr, H, x, ldx, cin, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns);
+    hipLaunchKernelGGL((k_kpconv_weighted_generic<INF, CLOSEST>), dim3((unsigned)cdiv64(nq * kKP, 256)), dim3(256), 0, st,
+                       q_pts, s_pts, nbr, H, x, ldx, cin, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns);
   }
   APR_LAUNCH_CHECK();
   return APR_OK;
 }
 
+APR_API int apr_kpconv_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
+                                int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream) {
+  return kpconv_weighted<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, kernel_points, n_kp, extent,
+                                                 rowsum, wf, ldwf, stream);
+}
+
+// apr_kpconv_weighted with the influence function (0 constant, 1 linear, 2 gaussian: blocks.py:320-337, 61-68) and the
+// aggregation (closest = 1: only the kernel point nearest to a neighbour keeps its influence, blocks.py:339-345).
+// (1, 0) launches what apr_kpconv_weighted launches: the same bits.
+APR_API int apr_kpconv_weighted_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                     int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
+                                     int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf,
+                                     int32_t influence, int32_t closest, void* stream) {
+  APR_CHECK_ARG(kpmode::valid(influence, closest),
+                "apr_kpconv_weighted_mode: influence must be 0, 1 or 2 and closest 0 or 1, got %d, %d", influence, closest);
+  APR_KP_MODE_DISPATCH(kpconv_weighted, q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, kernel_points, n_kp, extent, rowsum, wf,
+                       ldwf, stream)
+}
+
+template <int INF, bool CLOSEST>
 static int kpconv_dfeat(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
                         const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
                         float extent, const float* rowsum, float* dx, int64_t lddx, float* contrib, void* stream) {
@@ -877,8 +954,8 @@ static int kpconv_dfeat(const float* q_pts, int64_t nq, const float* s_pts, int6
   if (nq == 0) return APR_OK;
   const unsigned grid = (unsigned)cdiv64(nq, 4);
 #define APR_DF(N)                                                                                                     \
-  hipLaunchKernelGGL(k_kpconv_dfeat<N>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, dwf, lddwf, cin, kernel_points, \
-                     extent, rowsum, dx, lddx, (int)nq, (int)ns, contrib)
+  hipLaunchKernelGGL((k_kpconv_dfeat<N, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, dwf, lddwf, cin, \
+                     kernel_points, extent, rowsum, dx, lddx, (int)nq, (int)ns, contrib)
   if (cin <= 64) APR_DF(1);
   else if (cin <= 128) APR_DF(2);
   else if (cin <= 256) APR_DF(4);
@@ -888,11 +965,19 @@ static int kpconv_dfeat(const float* q_pts, int64_t nq, const float* s_pts, int6
   return APR_OK;
 }
 
+template <int INF, bool CLOSEST>
+static int kpconv_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
+                                float extent, const float* rowsum, float* contrib, void* stream) {
+  return kpconv_dfeat<INF, CLOSEST>(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp, extent, rowsum, contrib,
+                                    cin, contrib, stream);
+}
+
 APR_API int apr_kpconv_dfeat(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
                              const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
                              float extent, const float* rowsum, float* dx, int64_t lddx, void* stream) {
-  return kpconv_dfeat(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp, extent, rowsum, dx, lddx, nullptr,
-                      stream);
+  return kpconv_dfeat<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp, extent,
+                                              rowsum, dx, lddx, nullptr, stream);
 }
 
 // The deterministic form: the per-(query, neighbour) contributions go to contrib f32 [nq * H, cin] (rows of padding
@@ -902,8 +987,22 @@ APR_API int apr_kpconv_dfeat_contrib(const float* q_pts, int64_t nq, const float
                                      int32_t H, const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points,
                                      int32_t n_kp, float extent, const float* rowsum, float* contrib, void* stream) {
   APR_CHECK_ARG(contrib != nullptr, "apr_kpconv_dfeat_contrib: null contribution buffer");
-  return kpconv_dfeat(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp, extent, rowsum, contrib, cin,
-                      contrib, stream);
+  return kpconv_dfeat_contrib<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp,
+                                                      extent, rowsum, contrib, stream);
+}
+
+// apr_kpconv_dfeat_contrib with the influence function and the aggregation of apr_kpconv_weighted_mode (blocks.py:320-345:
+// d x flows through whichever influences the forward used; the closest kernel point is the forward's, kpmode::closest_kp).
+// (1, 0) launches what apr_kpconv_dfeat_contrib launches: the same bits.
+APR_API int apr_kpconv_dfeat_contrib_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                          int32_t H, const float* dwf, int64_t lddwf, int32_t cin,
+                                          const float* kernel_points, int32_t n_kp, float extent, const float* rowsum,
+                                          float* contrib, int32_t influence, int32_t closest, void* stream) {
+  APR_CHECK_ARG(kpmode::valid(influence, closest),
+                "apr_kpconv_dfeat_contrib_mode: influence must be 0, 1 or 2 and closest 0 or 1, got %d, %d", influence, closest);
+  APR_CHECK_ARG(contrib != nullptr, "apr_kpconv_dfeat_contrib_mode: null contribution buffer");
+  APR_KP_MODE_DISPATCH(kpconv_dfeat_contrib, q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, kernel_points, n_kp, extent, rowsum,
+                       contrib, stream)
 }
 
 APR_API int apr_gather_pool(const float* x, int64_t ldx, int64_t ns, int32_t c, const int32_t* inds, int32_t H,

@@ -22,7 +22,15 @@
 //
 // All three kernels: one wave per query, 4 per block, n_kp = 15, cin % 64 == 0, cin <= 512, 1 <= H <= 128, 16-byte
 // aligned rows; every sum in a fixed order (no atomics): the same bits on every run.
+//
+// Influence and aggregation (blocks.py:320-345) are compile-time parameters INF / CLOSEST of all three kernels; <kLinear,
+// false> is the code above.  For the constant and the gaussian influence the reference's re-gather DOES matter: a real
+// neighbour outside every deformed ball contributes nothing (in_range masks w), one inside a ball carries its influence to
+// all 15 kernel points, or with CLOSEST to its nearest one alone (kpmode::closest_kp, the same statement in every kernel).
+//   gaussian: w = exp(-d2 / (2 sigma^2 + 1e-9)), sigma = 0.3 extent;  d_dkp = mod / num * sum_{h in range} w 2 diff / (2 sigma^2 + 1e-9) P
+//   constant: w = 1;  d_dkp = 0
 #include "common.h"
+#include "kpconv_modes.h"
 
 namespace {
 
@@ -35,7 +43,9 @@ constexpr float kShadow = 1e6f;
 // dkp[q, r16], B = one 16-byte gather per lane.  New: a geometry pass before the channel passes gives, per step of 4
 // neighbours, the in-range flags (one ballot: the 16 lanes of a k-slot hold the 15 kernel points of its neighbour), the
 // count from them, and the running minimum of d2 per kernel point (reduced over the four k-slot lane groups at the end).
-template <int NG>
+// With a mode other than <kLinear, false> the lane that stages slot h also records the slot's mode byte (closest kernel
+// point, in-range flag) for the channel passes.
+template <int NG, int INF = kpmode::kLinear, bool CLOSEST = false>
 __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
     const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
     const float* __restrict__ x, int64_t ldx, int cin, const float* __restrict__ dkp, const float* __restrict__ mod,
@@ -43,6 +53,8 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
     int nq, int ns, int xcd_swz) {
   __shared__ int s_idx[4][kMaxH];          // >= 0: support row; -1: padding; bit 30 of a real row: positive feature sum
   __shared__ float s_diff[4][kMaxH][3];
+  constexpr bool MODE = CLOSEST || INF != kpmode::kLinear;
+  __shared__ unsigned char s_cl[MODE ? 4 : 1][MODE ? kMaxH : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, qd = lane >> 4;
   int blk = blockIdx.x;
@@ -67,9 +79,12 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
     }
     s_idx[wave][h] = idx;
     s_diff[wave][h][0] = dx; s_diff[wave][h][1] = dy; s_diff[wave][h][2] = dz;
+    if constexpr (MODE)
+      s_cl[wave][h] = idx >= 0 ? (unsigned char)kpmode::closest_kp(dx, dy, dz, dkp + (int64_t)qi * kKP * 3, extent * extent) : 0;
   }
   // (the wave's LDS writes are read back by other lanes of the same wave: in-order LDS queue, no barrier needed)
   const float inv_extent = 1.f / extent, ext2 = extent * extent;
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   const bool kvalid = r16 < kKP;
   const float* kq = dkp + ((int64_t)qi * kKP + (kvalid ? r16 : 0)) * 3;
   const float kx = kq[0], ky = kq[1], kz = kq[2];
@@ -109,7 +124,12 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
       float w = 0.f;
       if (kvalid && raw >= 0) {
         const float ex = s_diff[wave][h][0] - kx, ey = s_diff[wave][h][1] - ky, ez = s_diff[wave][h][2] - kz;
-        w = fmaxf(1.f - sqrtf(ex * ex + ey * ey + ez * ez) * inv_extent, 0.f);
+        if constexpr (INF == kpmode::kLinear) {
+          w = fmaxf(1.f - sqrtf(ex * ex + ey * ey + ez * ez) * inv_extent, 0.f);
+        } else {      // only the neighbours inside some deformed ball take part (blocks.py:298-316)
+          w = (s_cl[wave][h] & kpmode::kInRange) ? kpmode::influence<INF>(ex * ex + ey * ey + ez * ez, inv_extent, gden) : 0.f;
+        }
+        if constexpr (CLOSEST) w = (s_cl[wave][h] & 15) == r16 ? w : 0.f;
       }
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -139,13 +159,16 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
 // The index stage the two backward kernels share: lane h of the wave fills slot h (idx, centred point, and for the
 // feature gradient the 15 influences) and the wave's in-range count comes back.  dkp[q] is read at wave-uniform
 // addresses.
-template <bool KEEP_W>
+// With a mode other than <kLinear, false>: the influences kept are the mode's (masked by the in-range flag unless linear,
+// and by the closest kernel point with CLOSEST); the geometry gradient gets the slot's mode byte in s_cl instead.
+template <bool KEEP_W, int INF = kpmode::kLinear, bool CLOSEST = false>
 __device__ inline int deform_index_stage(const float* __restrict__ q_pts, const float* __restrict__ s_pts,
                                          const int* __restrict__ nbr, int H, const float* __restrict__ kq, float extent,
                                          const float* __restrict__ rowsum, int qi, int ns, int lane, int* s_idx,
-                                         float (*s_diff)[3], float (*s_w)[16]) {
+                                         float (*s_diff)[3], float (*s_w)[16], unsigned char* s_cl = nullptr) {
   const float qx = q_pts[3 * (int64_t)qi], qy = q_pts[3 * (int64_t)qi + 1], qz = q_pts[3 * (int64_t)qi + 2];
   const float inv_extent = 1.f / extent, ext2 = extent * extent;
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   int cnt = 0;
   for (int h = lane; h < kMaxH; h += 64) {
     int idx = -1;
@@ -159,12 +182,29 @@ __device__ inline int deform_index_stage(const float* __restrict__ q_pts, const 
       dy = s_pts[3 * (int64_t)idx + 1] - qy;
       dz = s_pts[3 * (int64_t)idx + 2] - qz;
       bool inr = false;
+      if constexpr (INF == kpmode::kLinear && !CLOSEST) {
 #pragma unroll
-      for (int k = 0; k < kKP; ++k) {
-        const float ex = dx - kq[3 * k], ey = dy - kq[3 * k + 1], ez = dz - kq[3 * k + 2];
-        const float d2 = ex * ex + ey * ey + ez * ez;
-        inr = inr || d2 < ext2;
-        if (KEEP_W) s_w[h][k] = fmaxf(1.f - sqrtf(d2) * inv_extent, 0.f);
+        for (int k = 0; k < kKP; ++k) {
+          const float ex = dx - kq[3 * k], ey = dy - kq[3 * k + 1], ez = dz - kq[3 * k + 2];
+          const float d2 = ex * ex + ey * ey + ez * ez;
+          inr = inr || d2 < ext2;
+          if (KEEP_W) s_w[h][k] = fmaxf(1.f - sqrtf(d2) * inv_extent, 0.f);
+        }
+      } else {
+        const int cl = kpmode::closest_kp(dx, dy, dz, kq, ext2);
+        inr = (cl & kpmode::kInRange) != 0;
+        if constexpr (KEEP_W) {
+#pragma unroll
+          for (int k = 0; k < kKP; ++k) {
+            const float ex = dx - kq[3 * k], ey = dy - kq[3 * k + 1], ez = dz - kq[3 * k + 2];
+            const float d2 = ex * ex + ey * ey + ez * ez;
+            float w = INF == kpmode::kLinear ? fmaxf(1.f - sqrtf(d2) * inv_extent, 0.f)
+                                             : (inr ? kpmode::influence<INF>(d2, inv_extent, gden) : 0.f);
+            s_w[h][k] = (!CLOSEST || k == (cl & 15)) ? w : 0.f;
+          }
+        } else {
+          s_cl[h] = (unsigned char)cl;
+        }
       }
       cnt += (inr && rowsum[idx] > 0.f) ? 1 : 0;
     }
@@ -177,7 +217,7 @@ __device__ inline int deform_index_stage(const float* __restrict__ q_pts, const 
 
 // Feature gradient, contribution rows: k_kpconv_dfeat (kpconv.hip) with the query's own kernel points, mod folded into
 // the 15 register values of a lane's channel, and the in-range count.
-template <int CPL>   // channels per lane: cin <= 64 * CPL
+template <int CPL, int INF = kpmode::kLinear, bool CLOSEST = false>   // channels per lane: cin <= 64 * CPL
 __global__ __launch_bounds__(256) void k_kpconv_deform_dfeat(
     const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
     const float* __restrict__ dwf, int64_t lddwf, int cin, const float* __restrict__ dkp, const float* __restrict__ mod,
@@ -187,8 +227,8 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_dfeat(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qi = blockIdx.x * 4 + wave;
   if (qi >= nq) return;
-  const int cnt = deform_index_stage<true>(q_pts, s_pts, nbr, H, dkp + (int64_t)qi * kKP * 3, extent, rowsum, qi, ns, lane,
-                                           s_idx[wave], nullptr, s_w[wave]);
+  const int cnt = deform_index_stage<true, INF, CLOSEST>(q_pts, s_pts, nbr, H, dkp + (int64_t)qi * kKP * 3, extent, rowsum, qi,
+                                                         ns, lane, s_idx[wave], nullptr, s_w[wave]);
   const float inv_num = 1.f / (float)max(cnt, 1);
   float g[CPL][kKP];
 #pragma unroll
@@ -228,6 +268,10 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_dfeat(
 // instruction (broadcast within each k-slot group).
 // The accumulator leaves lane (k = r16, qd) with P[h = 16 t + 4 qd + i][k]: it combines them with ITS kernel point's
 // diff / (d extent) and w in ascending (t, i), the four qd groups meet by two shuffles: a fixed order.
+// Modes: the term of (h, k) exists for the neighbours in range (and, with CLOSEST, for the neighbour's closest kernel point
+// alone: the one-hot mask is a constant of the graph).  gaussian: d_mod += w P, d_dkp += w 2 diff / (2 sigma^2 + 1e-9) P -- no
+// singularity at d = 0, so no term is left out there; constant: d_mod += P, d_dkp = 0 exactly.
+template <int INF = kpmode::kLinear, bool CLOSEST = false>
 __global__ __launch_bounds__(256) void k_kpconv_deform_dgeom(
     const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
     const float* __restrict__ x, int64_t ldx, int cin, const float* __restrict__ dwf, int64_t lddwf,
@@ -235,13 +279,15 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_dgeom(
     float* __restrict__ d_dkp, float* __restrict__ d_mod, int nq, int ns) {
   __shared__ int s_idx[4][kMaxH];
   __shared__ float s_diff[4][kMaxH][3];
+  constexpr bool MODE = CLOSEST || INF != kpmode::kLinear;
+  __shared__ unsigned char s_cl[MODE ? 4 : 1][MODE ? kMaxH : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, qd = lane >> 4;
   const int qi = blockIdx.x * 4 + wave;
   if (qi >= nq) return;
   const float* kq = dkp + (int64_t)qi * kKP * 3;
-  const int cnt = deform_index_stage<false>(q_pts, s_pts, nbr, H, kq, extent, rowsum, qi, ns, lane, s_idx[wave],
-                                            s_diff[wave], nullptr);
+  const int cnt = deform_index_stage<false, INF, CLOSEST>(q_pts, s_pts, nbr, H, kq, extent, rowsum, qi, ns, lane, s_idx[wave],
+                                                          s_diff[wave], nullptr, s_cl[MODE ? wave : 0]);
   const float inv_num = 1.f / (float)max(cnt, 1);
   const bool kvalid = r16 < kKP;
   const int ntile = (H + 15) >> 4;
@@ -273,6 +319,7 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_dgeom(
     }
   }
   const float inv_extent = 1.f / extent;
+  [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   const float kx = kvalid ? kq[3 * r16] : 0.f, ky = kvalid ? kq[3 * r16 + 1] : 0.f, kz = kvalid ? kq[3 * r16 + 2] : 0.f;
   float gx = 0.f, gy = 0.f, gz = 0.f, gm = 0.f;
 #pragma unroll
@@ -283,14 +330,33 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_dgeom(
         const int h = t * 16 + 4 * qd + i;
         if (s_idx[wave][h] >= 0) {      // real (slots behind H hold -1)
           const float ex = s_diff[wave][h][0] - kx, ey = s_diff[wave][h][1] - ky, ez = s_diff[wave][h][2] - kz;
-          const float d = sqrtf(ex * ex + ey * ey + ez * ez);
-          const float w = 1.f - d * inv_extent;
-          if (w > 0.f) {
-            const float p = acc[t][i];
-            gm = fmaf(w, p, gm);
-            if (d > 0.f) {
-              const float f = p / (d * extent);
-              gx = fmaf(ex, f, gx); gy = fmaf(ey, f, gy); gz = fmaf(ez, f, gz);
+          if constexpr (INF == kpmode::kLinear) {
+            const float d = sqrtf(ex * ex + ey * ey + ez * ez);
+            const float w = 1.f - d * inv_extent;
+            bool live = w > 0.f;
+            if constexpr (CLOSEST) live = live && (s_cl[wave][h] & 15) == r16;
+            if (live) {
+              const float p = acc[t][i];
+              gm = fmaf(w, p, gm);
+              if (d > 0.f) {
+                const float f = p / (d * extent);
+                gx = fmaf(ex, f, gx); gy = fmaf(ey, f, gy); gz = fmaf(ez, f, gz);
+              }
+            }
+          } else {
+            const int cl = s_cl[wave][h];
+            bool live = (cl & kpmode::kInRange) != 0;
+            if constexpr (CLOSEST) live = live && (cl & 15) == r16;
+            if (live) {
+              const float p = acc[t][i];
+              if constexpr (INF == kpmode::kGaussian) {
+                const float w = kpmode::influence<INF>(ex * ex + ey * ey + ez * ez, inv_extent, gden);
+                gm = fmaf(w, p, gm);
+                const float f = w * (2.f / gden) * p;
+                gx = fmaf(ex, f, gx); gy = fmaf(ey, f, gy); gz = fmaf(ez, f, gz);
+              } else {
+                gm += p;      // constant influence: no dependence on the kernel point's position
+              }
             }
           }
         }
@@ -317,10 +383,16 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
                 fn ": needs cin %% 64 == 0, cin <= 512, 1 <= H <= %d, ns > 0, extent > 0", kMaxH);                     \
   APR_CHECK_ARG(q_pts && s_pts && nbr && dkp && rowsum, fn ": null argument")
 
-APR_API int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
-                                       int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dkp,
-                                       const float* mod, int32_t n_kp, float extent, const float* rowsum, float* wf,
-                                       int64_t ldwf, float* min_d2, void* stream) {
+static int deform_xcd() {
+  static const int s_xcd = env_int("APR_KPCONV_XCD", 1);      // A/B switch (shared with apr_kpconv_weighted)
+  return s_xcd;
+}
+
+// One body per entry point for the old signature (<kLinear, false>: the launches it always made) and its _mode form.
+template <int INF, bool CLOSEST>
+static int deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                           const float* x, int64_t ldx, int32_t cin, const float* dkp, const float* mod, int32_t n_kp,
+                           float extent, const float* rowsum, float* wf, int64_t ldwf, float* min_d2, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_DEFORM_SHAPE("apr_kpconv_deform_weighted");
   APR_CHECK_ARG(x && wf && ldx >= cin && ldwf >= (int64_t)kKP * cin && ldx % 4 == 0 && ldwf % 4 == 0 && aligned16(x) &&
@@ -328,10 +400,10 @@ APR_API int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const flo
                 "apr_kpconv_deform_weighted: x / wf rows must be 16-byte aligned and at least cin / 15 cin wide");
   if (nq == 0) return APR_OK;
   const unsigned grid = (unsigned)cdiv64(nq, 4);
-  static const int s_xcd = env_int("APR_KPCONV_XCD", 1);      // A/B switch (shared with apr_kpconv_weighted)
+  const int s_xcd = deform_xcd();
 #define APR_DW(N)                                                                                                       \
-  hipLaunchKernelGGL(k_kpconv_deform_weighted<N>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, cin, dkp, mod, \
-                     extent, rowsum, wf, ldwf, min_d2, (int)nq, (int)ns, s_xcd)
+  hipLaunchKernelGGL((k_kpconv_deform_weighted<N, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, \
+                     cin, dkp, mod, extent, rowsum, wf, ldwf, min_d2, (int)nq, (int)ns, s_xcd)
   if (cin >= 256) APR_DW(4);
   else if (cin == 128) APR_DW(2);
   else APR_DW(1);
@@ -340,10 +412,35 @@ APR_API int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const flo
   return APR_OK;
 }
 
-APR_API int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                                            const int32_t* nbr, int32_t H, const float* dwf, int64_t lddwf, int32_t cin,
-                                            const float* dkp, const float* mod, int32_t n_kp, float extent,
-                                            const float* rowsum, float* contrib, void* stream) {
+APR_API int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                       int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dkp,
+                                       const float* mod, int32_t n_kp, float extent, const float* rowsum, float* wf,
+                                       int64_t ldwf, float* min_d2, void* stream) {
+  return deform_weighted<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dkp, mod, n_kp, extent, rowsum, wf,
+                                                 ldwf, min_d2, stream);
+}
+
+#define APR_DEFORM_MODE(fn)                                                                                            \
+  APR_CHECK_ARG(kpmode::valid(influence, closest), fn ": influence must be 0, 1 or 2 and closest 0 or 1, got %d, %d", \
+                influence, closest)
+
+// apr_kpconv_deform_weighted with the influence function (0 constant, 1 linear, 2 gaussian: blocks.py:320-337, 61-68) and
+// the aggregation (closest = 1: blocks.py:339-345).  For the constant and the gaussian influence only the neighbours inside
+// some deformed ball take part (the re-gather of blocks.py:298-316).  (1, 0) launches what apr_kpconv_deform_weighted
+// launches: the same bits.
+APR_API int apr_kpconv_deform_weighted_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                            int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dkp,
+                                            const float* mod, int32_t n_kp, float extent, const float* rowsum, float* wf,
+                                            int64_t ldwf, float* min_d2, int32_t influence, int32_t closest, void* stream) {
+  APR_DEFORM_MODE("apr_kpconv_deform_weighted_mode");
+  APR_KP_MODE_DISPATCH(deform_weighted, q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dkp, mod, n_kp, extent, rowsum, wf, ldwf,
+                       min_d2, stream)
+}
+
+template <int INF, bool CLOSEST>
+static int deform_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                const float* dwf, int64_t lddwf, int32_t cin, const float* dkp, const float* mod,
+                                int32_t n_kp, float extent, const float* rowsum, float* contrib, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_DEFORM_SHAPE("apr_kpconv_deform_dfeat_contrib");
   APR_CHECK_ARG(dwf && contrib && lddwf >= (int64_t)kKP * cin,
@@ -351,8 +448,8 @@ APR_API int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, cons
   if (nq == 0) return APR_OK;
   const unsigned grid = (unsigned)cdiv64(nq, 4);
 #define APR_DF(N)                                                                                                       \
-  hipLaunchKernelGGL(k_kpconv_deform_dfeat<N>, dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, dwf, lddwf, cin, dkp, mod, \
-                     extent, rowsum, (int)nq, (int)ns, contrib)
+  hipLaunchKernelGGL((k_kpconv_deform_dfeat<N, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, dwf, lddwf, \
+                     cin, dkp, mod, extent, rowsum, (int)nq, (int)ns, contrib)
   if (cin <= 64) APR_DF(1);
   else if (cin <= 128) APR_DF(2);
   else if (cin <= 256) APR_DF(4);
@@ -362,18 +459,60 @@ APR_API int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, cons
   return APR_OK;
 }
 
-APR_API int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
-                                    int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf,
-                                    const float* dkp, const float* mod, int32_t n_kp, float extent, const float* rowsum,
-                                    float* d_dkp, float* d_mod, void* stream) {
+APR_API int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
+                                            const int32_t* nbr, int32_t H, const float* dwf, int64_t lddwf, int32_t cin,
+                                            const float* dkp, const float* mod, int32_t n_kp, float extent,
+                                            const float* rowsum, float* contrib, void* stream) {
+  return deform_dfeat_contrib<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, dkp, mod, n_kp, extent,
+                                                      rowsum, contrib, stream);
+}
+
+// apr_kpconv_deform_dfeat_contrib with the mode of apr_kpconv_deform_weighted_mode: d x flows through the influences the
+// forward used (blocks.py:320-358), in-range filter and closest kernel point included.  (1, 0): the same bits as the old entry.
+APR_API int apr_kpconv_deform_dfeat_contrib_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
+                                                 const int32_t* nbr, int32_t H, const float* dwf, int64_t lddwf, int32_t cin,
+                                                 const float* dkp, const float* mod, int32_t n_kp, float extent,
+                                                 const float* rowsum, float* contrib, int32_t influence, int32_t closest,
+                                                 void* stream) {
+  APR_DEFORM_MODE("apr_kpconv_deform_dfeat_contrib_mode");
+  APR_KP_MODE_DISPATCH(deform_dfeat_contrib, q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, dkp, mod, n_kp, extent, rowsum,
+                       contrib, stream)
+}
+
+template <int INF, bool CLOSEST>
+static int deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                        const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
+                        const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
+                        void* stream) {
   hipStream_t st = (hipStream_t)stream;
   APR_DEFORM_SHAPE("apr_kpconv_deform_dgeom");
   APR_CHECK_ARG(x && dwf && d_dkp && d_mod && ldx >= cin && lddwf >= (int64_t)kKP * cin && ldx % 4 == 0 && lddwf % 4 == 0 &&
                     aligned16(x) && aligned16(dwf),
                 "apr_kpconv_deform_dgeom: x / dwf rows must be 16-byte aligned and at least cin / 15 cin wide");
   if (nq == 0) return APR_OK;
-  hipLaunchKernelGGL(k_kpconv_deform_dgeom, dim3((unsigned)cdiv64(nq, 4)), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx,
-                     cin, dwf, lddwf, dkp, mod, extent, rowsum, d_dkp, d_mod, (int)nq, (int)ns);
+  hipLaunchKernelGGL((k_kpconv_deform_dgeom<INF, CLOSEST>), dim3((unsigned)cdiv64(nq, 4)), dim3(256), 0, st, q_pts, s_pts, nbr,
+                     H, x, ldx, cin, dwf, lddwf, dkp, mod, extent, rowsum, d_dkp, d_mod, (int)nq, (int)ns);
   APR_LAUNCH_CHECK();
   return APR_OK;
+}
+
+APR_API int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                    int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf,
+                                    const float* dkp, const float* mod, int32_t n_kp, float extent, const float* rowsum,
+                                    float* d_dkp, float* d_mod, void* stream) {
+  return deform_dgeom<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dwf, lddwf, dkp, mod, n_kp, extent,
+                                              rowsum, d_dkp, d_mod, stream);
+}
+
+// apr_kpconv_deform_dgeom with the mode of apr_kpconv_deform_weighted_mode (the graph of blocks.py:284-358 differentiated
+// with respect to deformed_KP and the modulations): linear as the old entry, masked by the closest kernel point's one-hot
+// when closest; gaussian d_dkp = mod / num * sum_{h in range} w 2 diff / (2 sigma^2 + 1e-9) P; constant d_dkp = 0 exactly;
+// d_mod = sum_h w P / num with the mode's w.  (1, 0): the same bits as the old entry.
+APR_API int apr_kpconv_deform_dgeom_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                         int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf,
+                                         const float* dkp, const float* mod, int32_t n_kp, float extent, const float* rowsum,
+                                         float* d_dkp, float* d_mod, int32_t influence, int32_t closest, void* stream) {
+  APR_DEFORM_MODE("apr_kpconv_deform_dgeom_mode");
+  APR_KP_MODE_DISPATCH(deform_dgeom, q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dwf, lddwf, dkp, mod, n_kp, extent, rowsum,
+                       d_dkp, d_mod, stream)
 }

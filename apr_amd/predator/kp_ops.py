@@ -199,8 +199,42 @@ def row_sums(x):
     return out
 
 
-def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent):
-    """KPConv step 1 -> weighted features [Nq, ld] (ld = 15*cin rounded up to 32), already / neighbour count."""
+INFLUENCES = {"constant": 0, "linear": 1, "gaussian": 2}      # KP_influence -> the `influence` argument of the *_mode entries
+AGGREGATIONS = {"sum": 0, "closest": 1}                        # aggregation_mode -> `closest`
+DEFAULT_MODE = (1, 0)      # linear influence, sum aggregation: the entry points without a mode
+
+
+def kpconv_mode(KP_influence, aggregation_mode):
+    """(KP_influence, aggregation_mode) of the reference's KPConv -> (influence, closest); ValueError with the reference's
+    messages (blocks.py:337, 345) for anything else."""
+    if KP_influence not in INFLUENCES:
+        raise ValueError('Unknown influence function type (config.KP_influence)')
+    if aggregation_mode not in AGGREGATIONS:
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    return INFLUENCES[KP_influence], AGGREGATIONS[aggregation_mode]
+
+
+def influence_torch(sq, extent, mode):
+    """The influences of blocks.py:320-345 on torch ops: sq [n, h, k] squared distances -> w [n, h, k].  Linear takes
+    sqrt(max(d2, 1e-30)): a zero geometry gradient for a neighbour exactly on a kernel point, as the kernels give; the
+    one-hot of the closest kernel point is a constant of the graph.  (The in-range filter of a deformable layer is the
+    caller's: it zeroes the features of the neighbours outside every ball.)"""
+    influence, closest = mode
+    if influence == 0:
+        w = torch.ones_like(sq)
+    elif influence == 1:
+        w = torch.clamp(1 - torch.sqrt(torch.clamp(sq, min=1e-30)) / extent, min=0.0)
+    else:
+        sigma = extent * 0.3
+        w = torch.exp(-sq / (2 * sigma ** 2 + 1e-9))
+    if closest:
+        w = w * torch.nn.functional.one_hot(torch.argmin(sq, dim=2), sq.shape[2]).to(w.dtype)
+    return w
+
+
+def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MODE):
+    """KPConv step 1 -> weighted features [Nq, ld] (ld = 15*cin rounded up to 32), already / neighbour count.
+    mode = (influence, closest): apr_kpconv_weighted_mode for anything but the default."""
     nbr = _i32(nbr, "kpconv.nbr")
     x, ldx = ops._rows(x, "kpconv.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -209,6 +243,12 @@ def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent):
     wf = torch.zeros((nq, ld), dtype=torch.float32, device=x.device) if ld != kk else \
         torch.empty((nq, ld), dtype=torch.float32, device=x.device)
     rs = row_sums(x)
+    if tuple(mode) != DEFAULT_MODE:
+        check(_lib.load().apr_kpconv_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
+                                                   nbr.shape[1], ptr(x), ldx, cin, ptr(kernel_points.contiguous()),
+                                                   kernel_points.shape[0], float(extent), ptr(rs), ptr(wf), ld, int(mode[0]),
+                                                   int(mode[1]), stream()))
+        return wf
     check(_lib.load().apr_kpconv_weighted(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1],
                                           ptr(x), ldx, cin, ptr(kernel_points.contiguous()), kernel_points.shape[0],
                                           float(extent), ptr(rs), ptr(wf), ld, stream()))
@@ -278,14 +318,17 @@ class KPConvFunction(torch.autograd.Function):
     forward   wf = step 1 (apr_kpconv_weighted), out = wf @ W (dense MFMA GEMM);
     d W       = wf^T @ dout                       (apr_spconv_wgrad, identity map; wf is recomputed, not stored);
     d x       = scatter of (dout @ W^T) through the influences (apr_kpconv_dfeat on the forward's neighbour table).
-    The points, the kernel points and the neighbour table get no gradient (rigid kernel)."""
+    The points, the kernel points and the neighbour table get no gradient (rigid kernel).
+    mode = (influence, closest): the *_mode entry points; d x of a mode other than the default exists in the deterministic
+    form only (apr_kpconv_dfeat_contrib_mode)."""
 
     @staticmethod
-    def forward(ctx, q_pts, s_pts, inds, x, weights, kernel_points, extent):
+    def forward(ctx, q_pts, s_pts, inds, x, weights, kernel_points, extent, mode=DEFAULT_MODE):
         inds = _i32(inds, "kpconv.nbr")
         x = x.contiguous()
         K, cin, cout = weights.shape
-        wf = kpconv_weighted(q_pts, s_pts, inds, x, kernel_points, extent)
+        ctx.mode = mode = (int(mode[0]), int(mode[1]))
+        wf = kpconv_weighted(q_pts, s_pts, inds, x, kernel_points, extent, mode)
         w2 = weights.detach().reshape(K * cin, cout)
         if wf.shape[1] != K * cin:
             w2 = torch.cat([w2, torch.zeros((wf.shape[1] - K * cin, cout), dtype=w2.dtype, device=w2.device)], 0)
@@ -301,7 +344,7 @@ class KPConvFunction(torch.autograd.Function):
         dout = dout.contiguous()
         dx = dw = None
         if ctx.needs_input_grad[4]:
-            wf = kpconv_weighted(q_pts, s_pts, inds, x, kernel_points, ctx.extent)
+            wf = kpconv_weighted(q_pts, s_pts, inds, x, kernel_points, ctx.extent, ctx.mode)
             dw = ops.spconv_wgrad(wf, dout, None, 1, wf.shape[1], cout)[0, :K * cin].reshape(K, cin, cout)
         if ctx.needs_input_grad[3]:
             dwf = linear(dout, pack_linear(weights.detach().reshape(K * cin, cout).t().contiguous(), bf3=False))   # [nq, K*cin]
@@ -322,17 +365,24 @@ class KPConvFunction(torch.autograd.Function):
                 qp, sp, kp = q_pts.contiguous(), s_pts.contiguous(), kernel_points.contiguous()
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    check(lib.apr_kpconv_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                       ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent, ptr(rs),
-                                                       ptr(contrib), stream()))
+                    if ctx.mode != DEFAULT_MODE:
+                        check(lib.apr_kpconv_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                                ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
+                                                                ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
+                    else:
+                        check(lib.apr_kpconv_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                           ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
+                                                           ptr(rs), ptr(contrib), stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             else:
+                if ctx.mode != DEFAULT_MODE:
+                    raise _lib.AprHipError("kpconv: the atomic d x (apr_kpconv_dfeat) is linear influence / sum aggregation only")
                 dx = torch.zeros_like(x)
                 check(lib.apr_kpconv_dfeat(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(inds), H, ptr(dwf),
                                            lddwf, cin, ptr(kernel_points.contiguous()), kernel_points.shape[0], ctx.extent,
                                            ptr(rs), ptr(dx), dx.stride(0), stream()))
-        return None, None, None, dx, dw, None, None
+        return None, None, None, dx, dw, None, None, None
 
 
 def deform_ok(x, cin, H, K=15):
@@ -341,9 +391,10 @@ def deform_ok(x, cin, H, K=15):
     return K == 15 and cin % 64 == 0 and 64 <= cin <= 512 and 1 <= H <= 128 and rows_aligned(x, cin)
 
 
-def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=True):
+def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=True, mode=DEFAULT_MODE):
     """Deformable KPConv step 1 (apr_kpconv_deform_weighted) -> (wf [nq, 15 * cin], min_d2 [nq, 15] or None).
-    dkp [nq, 15, 3]: the query's own kernel points; mod [nq, 15] or None; wf is already mod / (in-range count)."""
+    dkp [nq, 15, 3]: the query's own kernel points; mod [nq, 15] or None; wf is already mod / (in-range count).
+    mode = (influence, closest): apr_kpconv_deform_weighted_mode for anything but the default."""
     nbr = _i32(nbr, "kpconv_deform.nbr")
     x, ldx = ops._rows(x, "kpconv_deform.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -354,6 +405,12 @@ def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=T
     wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=x.device)
     md = torch.empty((nq, 15), dtype=torch.float32, device=x.device) if want_min_d2 else None
     rs = row_sums(x)
+    if tuple(mode) != DEFAULT_MODE:
+        check(_lib.load().apr_kpconv_deform_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
+                                                          nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent),
+                                                          ptr(rs), ptr(wf), wf.stride(0), ptr(md), int(mode[0]), int(mode[1]),
+                                                          stream()))
+        return wf, md
     check(_lib.load().apr_kpconv_deform_weighted(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
                                                  nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent), ptr(rs),
                                                  ptr(wf), wf.stride(0), ptr(md), stream()))
@@ -368,14 +425,17 @@ class KPConvDeformFunction(torch.autograd.Function):
     d W       = wf^T @ dout (apr_spconv_wgrad; wf recomputed);
     d x       = apr_kpconv_deform_dfeat_contrib + apr_reverse_gather_range in DX_CHUNK_BYTES chunks (deterministic);
     d dkp, d mod = apr_kpconv_deform_dgeom.
-    The in-range count is a constant of the graph.  The points and the neighbour table get no gradient."""
+    The in-range count is a constant of the graph.  The points and the neighbour table get no gradient.
+    mode = (influence, closest): the *_mode entry points.  With the constant influence dkp gets None as its gradient, as in
+    the reference's graph (the kernel's d_dkp is exactly 0)."""
 
     @staticmethod
-    def forward(ctx, q_pts, s_pts, inds, x, weights, dkp, mod, extent):
+    def forward(ctx, q_pts, s_pts, inds, x, weights, dkp, mod, extent, mode=DEFAULT_MODE):
         inds = _i32(inds, "kpconv_deform.nbr")
         x = x.contiguous()
         K, cin, cout = weights.shape
-        wf, md = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, extent)
+        ctx.mode = mode = (int(mode[0]), int(mode[1]))
+        wf, md = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, extent, mode=mode)
         out = linear(wf, pack_linear(weights.detach().reshape(K * cin, cout), bf3=False))
         ctx.save_for_backward(q_pts, s_pts, inds, x, weights, dkp, mod)
         ctx.extent = float(extent)
@@ -389,9 +449,10 @@ class KPConvDeformFunction(torch.autograd.Function):
         dout = dout.contiguous()
         dx = dw = ddkp = dmod = None
         if ctx.needs_input_grad[4]:
-            wf, _ = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, ctx.extent, want_min_d2=False)
+            wf, _ = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, ctx.extent, want_min_d2=False, mode=ctx.mode)
             dw = ops.spconv_wgrad(wf, dout, None, 1, wf.shape[1], cout)[0].reshape(K, cin, cout)
-        need_geom = ctx.needs_input_grad[5] or (mod is not None and ctx.needs_input_grad[6])
+        moded = ctx.mode != DEFAULT_MODE
+        need_geom = (ctx.needs_input_grad[5] and ctx.mode[0] != 0) or (mod is not None and ctx.needs_input_grad[6])
         if ctx.needs_input_grad[3] or need_geom:
             dwf = linear(dout, pack_linear(weights.detach().reshape(K * cin, cout).t().contiguous(), bf3=False))
             dwf, lddwf = ops._rows(dwf, "kpconv_deform.dwf")
@@ -410,21 +471,34 @@ class KPConvDeformFunction(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    check(lib.apr_kpconv_deform_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                              ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
-                                                              ptr(None if md is None else md[q0:q1]), 15, ctx.extent, ptr(rs),
-                                                              ptr(contrib), stream()))
+                    if moded:
+                        check(lib.apr_kpconv_deform_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                                       ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
+                                                                       ptr(None if md is None else md[q0:q1]), 15, ctx.extent,
+                                                                       ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
+                    else:
+                        check(lib.apr_kpconv_deform_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                                  ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
+                                                                  ptr(None if md is None else md[q0:q1]), 15, ctx.extent, ptr(rs),
+                                                                  ptr(contrib), stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             if need_geom:
                 ddkp = torch.empty((nq, 15, 3), dtype=torch.float32, device=x.device)
                 dmod = torch.empty((nq, 15), dtype=torch.float32, device=x.device)
-                check(lib.apr_kpconv_deform_dgeom(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin, ptr(dwf),
-                                                  lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp), ptr(dmod),
-                                                  stream()))
+                if moded:
+                    check(lib.apr_kpconv_deform_dgeom_mode(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin,
+                                                           ptr(dwf), lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp),
+                                                           ptr(dmod), ctx.mode[0], ctx.mode[1], stream()))
+                else:
+                    check(lib.apr_kpconv_deform_dgeom(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin, ptr(dwf),
+                                                      lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp), ptr(dmod),
+                                                      stream()))
                 if mod is None:
                     dmod = None
-        return None, None, None, dx, dw, ddkp, dmod, None
+                if ctx.mode[0] == 0:
+                    ddkp = None
+        return None, None, None, dx, dw, ddkp, dmod, None, None
 
 
 def gather_pool(x, inds, mode, out=None):

@@ -4,7 +4,9 @@ Module names, constructor arguments and parameter names follow
 /root/reference/Predator_APR/models/blocks.py (KPConv :134-379, BatchNormBlock :436-474,
 UnaryBlock :477-510, LastUnaryBlock :513-536, SimpleBlock :539-593, ResnetBottleneckBlock :596-681,
 NearestUpsampleBlock :697-712, MaxPoolBlock :715-726, block_decider :385-433), so a reference
-state_dict loads unchanged.  KPConv is implemented for KP_influence 'linear' and aggregation 'sum' (other settings raise),
+state_dict loads unchanged.  KPConv takes the reference's three influences ('constant', 'linear', 'gaussian') and two
+aggregations ('sum', 'closest'; DESIGN section 34 -- behind KPCONV_MODES / APR_KPCONV_MODES=1, off by default; the fused
+forward and the one-call block plan are linear / sum only),
 rigid and deformable / modulated (blocks.py:235-316: a rigid offset_conv moves the 15 kernel points of every query and,
 when modulated, scales their features; kernels in csrc/kpconv_deform.hip).
 Inference runs the HIP kernels; when autograd is recording (training) every block switches
@@ -26,6 +28,9 @@ from ..kernels.kernel_points import load_kernels
 FUSED_BLOCK = os.environ.get("APR_KP_FUSED_BLOCK", "1") != "0"     # A/B switch: 0 = one library call per op of a block
 KPCONV_TRAIN_HIP = os.environ.get("APR_KPCONV_TRAIN_HIP", "1") != "0"   # A/B switch: 0 = KPConv's training path on torch ops
 KPCONV_DEFORM_HIP = os.environ.get("APR_KPCONV_DEFORM_HIP", "1") != "0"   # A/B switch: 0 = the deformed convolution on torch ops
+# 1 = KPConv builds with the constant / gaussian influence and the closest aggregation; 0 (default): the
+# constructor refuses them with NotImplementedError as before
+KPCONV_MODES = os.environ.get("APR_KPCONV_MODES", "0") != "0"
 # the fused KPConv forward (apr_kpconv_fused): 0 = never, 1 = where apr_kpconv_fused_route says so, 2 = wherever it can run
 FUSED_KPCONV = int(os.environ.get("APR_KPCONV_FUSED", "0") or 0)
 KPCONV_ROUTE_HOOK = None     # set to a callable(KPConv module, nq, cin, cout, H) to observe every fused-route decision
@@ -62,9 +67,18 @@ def closest_pool(x, inds, out=None):
 class KPConv(nn.Module):
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius, fixed_kernel_points='center',
                  KP_influence='linear', aggregation_mode='sum', deformable=False, modulated=False):
+        """KP_influence 'constant' | 'linear' | 'gaussian' and aggregation_mode 'sum' | 'closest' as in the reference
+        (blocks.py:149-150, 320-345); anything else raises ValueError with the reference's message -- here at construction,
+        the reference at the first forward.  A combination other than linear / sum builds when KPCONV_MODES is on
+        (APR_KPCONV_MODES=1) and raises NotImplementedError, as it always did, when it is off (the default: an existing test
+        holds the constructor to that).  offset_conv inherits both.  With the constant influence the deformed kernel
+        points take no gradient: offset_conv's weights (and offset_bias when not modulated) end with .grad None, as in the
+        reference."""
         super().__init__()
-        if KP_influence != 'linear' or aggregation_mode != 'sum':
-            raise NotImplementedError("HIP KPConv: linear influence / sum aggregation only (the APR configs)")
+        self._mode = kp_ops.kpconv_mode(KP_influence, aggregation_mode)      # (influence, closest) of the *_mode entries
+        if self._mode != kp_ops.DEFAULT_MODE and not KPCONV_MODES:
+            raise NotImplementedError("HIP KPConv: influence / aggregation other than linear / sum are behind a switch: set "
+                                      "APR_KPCONV_MODES=1 (or blocks.KPCONV_MODES = True) to build this layer")
         self.K, self.p_dim = kernel_size, p_dim
         self.in_channels, self.out_channels = in_channels, out_channels
         self.radius, self.KP_extent = radius, KP_extent
@@ -112,6 +126,8 @@ class KPConv(nn.Module):
         in_channels features on 16-byte boundaries) and, at FUSED_KPCONV = 1, the measured route table."""
         if not FUSED_KPCONV or self.deformable or self.K != 15 or nq <= 0 or not aligned or not kp_ops.DENSE_BF3:
             return False
+        if self._mode != kp_ops.DEFAULT_MODE:      # apr_kpconv_fused is linear influence / sum aggregation only
+            return False
         lib = _lib.load()
         if not lib.apr_kpconv_fused_ok(self.in_channels, self.out_channels, int(H)):
             return False
@@ -130,8 +146,13 @@ class KPConv(nn.Module):
             # [N, 15] weighted features) run on HIP as well
             if (self.in_channels % 64 == 0 or not x.requires_grad) and neighb_inds.shape[1] <= 128 \
                     and self.out_channels % 32 == 0 and KPCONV_TRAIN_HIP:
-                return kp_ops.KPConvFunction.apply(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points,
-                                                   self.KP_extent)
+                if self._mode == kp_ops.DEFAULT_MODE:
+                    return kp_ops.KPConvFunction.apply(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points,
+                                                       self.KP_extent)
+                # the other modes have the deterministic d x only (apr_kpconv_dfeat_contrib_mode)
+                if not x.requires_grad or (kp_ops.DET_DX and q_pts.shape[0] * neighb_inds.shape[1] < (1 << 31)):
+                    return kp_ops.KPConvFunction.apply(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points,
+                                                       self.KP_extent, self._mode)
             return self._forward_autograd(q_pts, s_pts, neighb_inds, x)       # other shapes: torch ops
         prof = kp_ops.PROFILE
         if prof is not None:      # bench.py roofline leg: HIP events on the launch stream around the layer's kernels
@@ -140,7 +161,7 @@ class KPConv(nn.Module):
         elif self._fused_route(q_pts.shape[0], neighb_inds.shape[1], kp_ops.rows_aligned(x, self.in_channels)) \
                 and self._weight()[5] is not None:
             return kp_ops.kpconv_fused(q_pts, s_pts, neighb_inds, x, self.kernel_points, self.KP_extent, self._weight())
-        wf = kp_ops.kpconv_weighted(q_pts, s_pts, neighb_inds, x, self.kernel_points, self.KP_extent)
+        wf = kp_ops.kpconv_weighted(q_pts, s_pts, neighb_inds, x, self.kernel_points, self.KP_extent, self._mode)
         out = kp_ops.linear(wf, self._weight())
         if prof is not None:
             e1.record()
@@ -148,11 +169,14 @@ class KPConv(nn.Module):
         return out
 
     def _forward_autograd(self, q_pts, s_pts, inds, x):
-        """blocks.py:229-374, rigid / linear influence / sum aggregation, with plain torch ops."""
+        """blocks.py:229-374 for a rigid layer with plain torch ops (every influence and aggregation)."""
         s_pad = torch.cat((s_pts, torch.zeros_like(s_pts[:1]) + 1e6), 0)
         neighbors = s_pad[inds.long()] - q_pts.unsqueeze(1)                          # [n, h, 3]
         sq = torch.sum((neighbors.unsqueeze(2) - self.kernel_points) ** 2, dim=3)      # [n, h, k]
-        w = torch.clamp(1 - torch.sqrt(sq) / self.KP_extent, min=0.0).transpose(1, 2)  # [n, k, h]
+        if self._mode == kp_ops.DEFAULT_MODE:
+            w = torch.clamp(1 - torch.sqrt(sq) / self.KP_extent, min=0.0).transpose(1, 2)  # [n, k, h]
+        else:
+            w = kp_ops.influence_torch(sq, self.KP_extent, self._mode).transpose(1, 2)
         nx = kp_ops.gather_pad(x, inds)                                              # [n, h, cin]
         weighted = torch.matmul(w, nx).permute(1, 0, 2)                              # [k, n, cin]
         out = torch.sum(torch.matmul(weighted, self.weights), dim=0)
@@ -179,10 +203,14 @@ class KPConv(nn.Module):
         if KPCONV_DEFORM_HIP and self.p_dim == 3 and kp_ops.deform_ok(x, self.in_channels, inds.shape[1], self.K) \
                 and q_pts.shape[0] > 0 and (not tracked or self.out_channels % 32 == 0):
             if tracked:
-                out, self.min_d2 = kp_ops.KPConvDeformFunction.apply(q_pts, s_pts, inds, x, self.weights, dkp, mod,
-                                                                     self.KP_extent)
+                if self._mode == kp_ops.DEFAULT_MODE:
+                    out, self.min_d2 = kp_ops.KPConvDeformFunction.apply(q_pts, s_pts, inds, x, self.weights, dkp, mod,
+                                                                         self.KP_extent)
+                else:
+                    out, self.min_d2 = kp_ops.KPConvDeformFunction.apply(q_pts, s_pts, inds, x, self.weights, dkp, mod,
+                                                                         self.KP_extent, self._mode)
                 return out
-            wf, self.min_d2 = kp_ops.kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, self.KP_extent)
+            wf, self.min_d2 = kp_ops.kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, self.KP_extent, mode=self._mode)
             return kp_ops.linear(wf, self._weight())
         return self._forward_autograd_deformable(q_pts, s_pts, inds, x, dkp, mod)
 
@@ -198,7 +226,10 @@ class KPConv(nn.Module):
         sq = torch.sum((neighbors.unsqueeze(2) - dkp.unsqueeze(1)) ** 2, dim=3)        # [n, h, k]
         self.min_d2 = torch.min(sq, dim=1)[0].detach()
         in_range = torch.any(sq < self.KP_extent ** 2, dim=2) & (idx < ns)             # [n, h]
-        w = torch.clamp(1 - torch.sqrt(torch.clamp(sq, min=1e-30)) / self.KP_extent, min=0.0).transpose(1, 2)
+        if self._mode == kp_ops.DEFAULT_MODE:
+            w = torch.clamp(1 - torch.sqrt(torch.clamp(sq, min=1e-30)) / self.KP_extent, min=0.0).transpose(1, 2)
+        else:     # the in-range mask on the features below is what keeps a constant / gaussian influence inside the balls
+            w = kp_ops.influence_torch(sq, self.KP_extent, self._mode).transpose(1, 2)
         nx = torch.cat((x, torch.zeros_like(x[:1])), 0)[idx] * in_range.unsqueeze(2).to(x.dtype)
         weighted = torch.matmul(w, nx)                                               # [n, k, cin]
         if mod is not None:
@@ -351,7 +382,7 @@ class ResnetBottleneckBlock(nn.Module):
     def _fused_ok(self, features, inds):
         """One library call for the whole block (apr_kp_resnet_block): inference, InstanceNorm blocks, widths that the
         bf16-split dense GEMM takes, rows 16-byte aligned.  APR_KP_FUSED_BLOCK=0 keeps the module-by-module path."""
-        return (FUSED_BLOCK and not self.KPConv.deformable and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
+        return (FUSED_BLOCK and not self.KPConv.deformable and self.KPConv._mode == kp_ops.DEFAULT_MODE and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
                 and kp_ops.DENSE_BF3 and self.in_dim % 64 == 0 and self.out_dim % 256 == 0 and features.is_cuda
                 and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1
                 and features.stride(0) % 4 == 0 and features.data_ptr() % 16 == 0 and inds.dtype == torch.int32

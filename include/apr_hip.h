@@ -1060,6 +1060,43 @@ int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, 
                             const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
                             const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
                             void* stream);
+/* KPConv's other influence functions and aggregation (Predator_APR/models/blocks.py:61-68, 320-345): the five entry points
+ * above with two more arguments, influence (0 constant, 1 linear, 2 gaussian) and closest (0 sum, 1 closest); with (1, 0)
+ * each launches exactly what its namesake launches (the same bits).  With d2 = |s[nbr[q,h]] - q - KP[q,k]|^2:
+ *   constant  w = 1 for every real (neighbour, kernel point)                                              (blocks.py:321-324)
+ *   linear    w = max(0, 1 - sqrt(d2) / extent)                                                          (blocks.py:326-329)
+ *   gaussian  w = exp(-d2 / (2 sigma^2 + 1e-9)), sigma = 0.3 extent, NOT clipped at the extent (expf)     (blocks.py:331-335)
+ *   closest   w[q,k,h] is kept for k = argmin_k d2[q,h,k] alone, the lowest k winning an exact tie (torch.argmin); the
+ *             one-hot mask is a constant of the graph (blocks.py:339-342).  Every kernel of a layer finds that kernel point
+ *             with the same float32 statement (kpconv_modes.h).
+ * Rigid layers (apr_kpconv_weighted_mode: blocks.py:320-372; apr_kpconv_dfeat_contrib_mode: the same lines differentiated
+ * with respect to x): every real neighbour takes part.  Deformable layers (apr_kpconv_deform_*_mode, blocks.py:292-358): only
+ * the neighbours inside some deformed ball (d2 < extent^2 for some k, blocks.py:298-316) take part -- for the constant and
+ * the gaussian influence a real neighbour outside every ball contributes nothing, one inside carries its influence to all
+ * 15 kernel points (sum) or to its closest one; min_d2, num and mod are as above.  apr_kpconv_deform_dgeom_mode: d_mod =
+ * sum_h w P / num with the mode's w; d_dkp linear as above (masked by the one-hot when closest), gaussian mod / num *
+ * sum_{h in range} w 2 diff / (2 sigma^2 + 1e-9) P (no singularity at d = 0: no deviation), constant exactly 0.
+ * Shapes, alignment and refusals as the namesakes; an influence outside 0..2 or closest outside 0..1 returns APR_EINVAL
+ * before any launch.  No atomics, fixed summation orders: the same bits on every run. */
+int apr_kpconv_weighted_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                             const float* x, int64_t ldx, int32_t cin, const float* kernel_points, int32_t n_kp, float extent,
+                             const float* rowsum, float* wf, int64_t ldwf, int32_t influence, int32_t closest, void* stream);
+int apr_kpconv_dfeat_contrib_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                  const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
+                                  float extent, const float* rowsum, float* contrib, int32_t influence, int32_t closest,
+                                  void* stream);
+int apr_kpconv_deform_weighted_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                    int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dkp, const float* mod,
+                                    int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, float* min_d2,
+                                    int32_t influence, int32_t closest, void* stream);
+int apr_kpconv_deform_dfeat_contrib_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                         int32_t H, const float* dwf, int64_t lddwf, int32_t cin, const float* dkp,
+                                         const float* mod, int32_t n_kp, float extent, const float* rowsum, float* contrib,
+                                         int32_t influence, int32_t closest, void* stream);
+int apr_kpconv_deform_dgeom_mode(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                 const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
+                                 const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
+                                 int32_t influence, int32_t closest, void* stream);
 size_t apr_reverse_table_scratch_bytes(int64_t nq, int32_t H, int64_t ns);
 int apr_reverse_table_build(const int32_t* nbr, int64_t nq, int32_t H, int64_t ns, int32_t* rev_t, int32_t* start,
                             void* scratch, size_t scratch_bytes, void* stream);
