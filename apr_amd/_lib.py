@@ -228,6 +228,7 @@ PROTOTYPES = {
     "apr_knn": (C.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "apr_row_sums": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "apr_kpconv_weighted": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _p]),
+    "apr_kpconv_weighted_c32": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _p]),
     "apr_kpconv_fused_ok": (_i32, [_i32, _i32, _i32]),
     "apr_kpconv_fused_route": (_i32, [_i64, _i32, _i32, _i32]),
     "apr_kpconv_fused": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i32, _p, _i64, _p]),

@@ -136,6 +136,86 @@ __global__ __launch_bounds__(256) void k_kpconv_weighted_mfma(
   }
 }
 
+// Step 1, MFMA form for Cin = 32 (the first layer of the symmetric generator KPFCNNDecoder reads the encoder's 32-d
+// descriptors on the FINEST level; linear influence, sum aggregation).  k_kpconv_weighted_mfma with a 128-byte feature row:
+// one wave per query, lane r16 gathers the float2 of channels 2 r16, 2 r16 + 1 (the 16 lanes of a k-slot read one row, the
+// four k-slots four neighbours), two column blocks cb <-> channel 2 r16 + cb, and D[k = 4 qd + i][col r16] leaves as one
+// float2 per kernel point.  The next step's two operands (index, centred point from LDS; the row from memory) are fetched
+// before the current step's MFMAs are issued.
+__global__ __launch_bounds__(256) void k_kpconv_weighted_c32(
+    const float* __restrict__ q_pts, const float* __restrict__ s_pts, const int* __restrict__ nbr, int H,
+    const float* __restrict__ x, int64_t ldx, const float* __restrict__ kp, float extent,
+    const float* __restrict__ rowsum, float* __restrict__ wf, int64_t ldwf, int nq, int ns, int xcd_swz) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  constexpr int kC = 32;
+  __shared__ int s_idx[4][kMaxH];
+  __shared__ float s_diff[4][kMaxH][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r16 = lane & 15, qd = lane >> 4;
+  int blk = blockIdx.x;
+  if (xcd_swz) {      // as k_kpconv_weighted_mfma: consecutive queries behind one XCD's L2
+    const int nb = gridDim.x, xcd = blk & 7, loc = blk >> 3;
+    blk = xcd * (nb >> 3) + min(xcd, nb & 7) + loc;
+  }
+  const int qi = blk * 4 + wave;
+  if (qi >= nq) return;
+  const float qx = q_pts[3 * (int64_t)qi], qy = q_pts[3 * (int64_t)qi + 1], qz = q_pts[3 * (int64_t)qi + 2];
+  int cnt = 0;
+  for (int h = lane; h < kMaxH; h += 64) {
+    int idx = -1;
+    float dx = 1e6f, dy = 1e6f, dz = 1e6f;
+    if (h < H) {
+      idx = nbr[(int64_t)qi * H + h];
+      if (idx >= 0 && idx < ns) {
+        dx = s_pts[3 * (int64_t)idx] - qx;
+        dy = s_pts[3 * (int64_t)idx + 1] - qy;
+        dz = s_pts[3 * (int64_t)idx + 2] - qz;
+        cnt += rowsum[idx] > 0.f ? 1 : 0;
+      } else {
+        idx = -1;  // shadow neighbour: no feature row, no influence, not counted
+      }
+    }
+    s_idx[wave][h] = idx;
+    s_diff[wave][h][0] = dx; s_diff[wave][h][1] = dy; s_diff[wave][h][2] = dz;
+  }
+  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+  const float inv_num = 1.f / (float)max(cnt, 1);
+  const float inv_extent = 1.f / extent;
+  const bool kvalid = r16 < kKP;
+  const float kx = kvalid ? kp[3 * r16] : 0.f, ky = kvalid ? kp[3 * r16 + 1] : 0.f, kz = kvalid ? kp[3 * r16 + 2] : 0.f;
+  const int nsteps = (H + 3) >> 2;      // 4 * nsteps <= kMaxH: every slot read below was staged above
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  auto fetch = [&](int st, int& idx, f32x2& b) {
+    idx = s_idx[wave][st * 4 + qd];
+    b = (f32x2){0.f, 0.f};
+    if (idx >= 0) b = *reinterpret_cast<const f32x2*>(x + (int64_t)idx * ldx + r16 * 2);
+  };
+  int idx;
+  f32x2 b;
+  fetch(0, idx, b);
+  for (int st = 0; st < nsteps; ++st) {
+    int idx_n = -1;
+    f32x2 b_n = {0.f, 0.f};
+    if (st + 1 < nsteps) fetch(st + 1, idx_n, b_n);
+    const int h = st * 4 + qd;
+    float w = 0.f;
+    if (kvalid && idx >= 0)
+      w = kp_weight(s_diff[wave][h][0], s_diff[wave][h][1], s_diff[wave][h][2], kx, ky, kz, inv_extent);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, b[0], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, b[1], acc1, 0, 0, 0);
+    idx = idx_n;
+    b = b_n;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int k = qd * 4 + i;
+    if (k < kKP) {
+      const f32x2 v = {acc0[i] * inv_num, acc1[i] * inv_num};
+      *reinterpret_cast<f32x2*>(wf + (int64_t)qi * ldwf + (int64_t)k * kC + r16 * 2) = v;
+    }
+  }
+}
+
 // Step 1, VALU form for any Cin (the first layer has Cin = 1).  One thread per (query, kernel point).  With CLOSEST every
 // thread finds the neighbour's closest kernel point itself (the one statement of it, kpmode::closest_kp).
 template <int INF = kpmode::kLinear, bool CLOSEST = false>
@@ -940,6 +1020,28 @@ APR_API int apr_kpconv_weighted_mode(const float* q_pts, int64_t nq, const float
                 "apr_kpconv_weighted_mode: influence must be 0, 1 or 2 and closest 0 or 1, got %d, %d", influence, closest);
   APR_KP_MODE_DISPATCH(kpconv_weighted, q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, kernel_points, n_kp, extent, rowsum, wf,
                        ldwf, stream)
+}
+
+// apr_kpconv_weighted for cin = 32 on the fp32 MFMA (k_kpconv_weighted_c32; linear influence, sum aggregation).  Unlike
+// apr_kpconv_weighted it has no other route: anything the kernel does not take is refused, and a refused call writes
+// nothing.
+APR_API int apr_kpconv_weighted_c32(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                    int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
+                                    int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream) {
+  APR_CHECK_ARG(n_kp == kKP, "apr_kpconv_weighted_c32: built for %d kernel points, got %d", kKP, n_kp);
+  APR_CHECK_ARG(cin == 32, "apr_kpconv_weighted_c32: built for 32 input channels, got %d", cin);
+  APR_CHECK_ARG(H > 0 && H <= kMaxH, "apr_kpconv_weighted_c32: 1 <= H <= %d, got %d", kMaxH, H);
+  APR_CHECK_ARG(nq >= 0 && nq <= INT32_MAX - 4 && ns > 0 && ns <= INT32_MAX && extent > 0.f,
+                "apr_kpconv_weighted_c32: bad arguments");
+  APR_CHECK_ARG(ldx >= cin && ldwf >= (int64_t)kKP * cin, "apr_kpconv_weighted_c32: leading dimension too small");
+  if (nq == 0) return APR_OK;
+  APR_CHECK_ARG(q_pts && s_pts && nbr && x && kernel_points && rowsum && wf, "apr_kpconv_weighted_c32: null pointer");
+  APR_CHECK_ARG(ldx % 2 == 0 && ldwf % 2 == 0 && ((((uintptr_t)x) | ((uintptr_t)wf)) & 7) == 0,
+                "apr_kpconv_weighted_c32: the rows of x and wf must start on 8-byte boundaries");
+  hipLaunchKernelGGL(k_kpconv_weighted_c32, dim3((unsigned)cdiv64(nq, 4)), dim3(256), 0, (hipStream_t)stream, q_pts, s_pts,
+                     nbr, H, x, ldx, kernel_points, extent, rowsum, wf, ldwf, (int)nq, (int)ns, kpconv_xcd());
+  APR_LAUNCH_CHECK();
+  return APR_OK;
 }
 
 template <int INF, bool CLOSEST>

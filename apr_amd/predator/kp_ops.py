@@ -232,9 +232,15 @@ def influence_torch(sq, extent, mode):
     return w
 
 
+# A/B switch: 0 sends cin = 32 (the first layer of KPFCNNDecoder) to apr_kpconv_weighted's generic kernel instead of
+# apr_kpconv_weighted_c32 (DESIGN section 35 has the measurement behind the default)
+KPCONV_C32 = os.environ.get("APR_KPCONV_C32", "1") != "0"
+
+
 def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MODE):
     """KPConv step 1 -> weighted features [Nq, ld] (ld = 15*cin rounded up to 32), already / neighbour count.
-    mode = (influence, closest): apr_kpconv_weighted_mode for anything but the default."""
+    mode = (influence, closest): apr_kpconv_weighted_mode for anything but the default.  Default mode, cin = 32, rows on
+    8-byte boundaries: apr_kpconv_weighted_c32 (KPCONV_C32)."""
     nbr = _i32(nbr, "kpconv.nbr")
     x, ldx = ops._rows(x, "kpconv.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -249,9 +255,12 @@ def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MO
                                                    kernel_points.shape[0], float(extent), ptr(rs), ptr(wf), ld, int(mode[0]),
                                                    int(mode[1]), stream()))
         return wf
-    check(_lib.load().apr_kpconv_weighted(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1],
-                                          ptr(x), ldx, cin, ptr(kernel_points.contiguous()), kernel_points.shape[0],
-                                          float(extent), ptr(rs), ptr(wf), ld, stream()))
+    entry = _lib.load().apr_kpconv_weighted
+    if KPCONV_C32 and cin == 32 and kernel_points.shape[0] == 15 and 1 <= nbr.shape[1] <= 128 and ldx % 2 == 0 \
+            and x.data_ptr() % 8 == 0:
+        entry = _lib.load().apr_kpconv_weighted_c32      # the MFMA correlation of the symmetric generator's first layer
+    check(entry(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1], ptr(x), ldx, cin,
+                ptr(kernel_points.contiguous()), kernel_points.shape[0], float(extent), ptr(rs), ptr(wf), ld, stream()))
     return wf
 
 

@@ -22,7 +22,7 @@ from ... import synth
 from ..configs.models import kitti_config
 from ..datasets import kitti
 from ..datasets.dataloader import calibrate_neighbors, collate_fn_descriptor
-from ..models.architectures import KPFCNN
+from ..models.architectures import KPFCNN, KPFCNNDecoder
 from ..models.mlp import GenerativeMLP_98
 from .tester import PredatorTestEpoch
 from .trainer import PredatorPairTrainStep
@@ -73,13 +73,22 @@ def synthetic_sample(dev, seed, config, split, n_beams=64, n_azimuth=1875, k=5, 
     return kitti.training_sample(up(xyz0), up(xyz1), cmpl[0], cmpl[1], poses[0], poses[1], T, config)
 
 
-def build_models(dev, config, seed=0):
-    """KPFCNN + GenerativeMLP_98 + the yaml's optimizer and scheduler, seeded."""
+def build_models(dev, config, seed=0, symmetric=False):
+    """KPFCNN + GenerativeMLP_98 + the yaml's optimizer and scheduler, seeded.  `symmetric`: the generator is a
+    KPFCNNDecoder built as the reference's main.py:52-63 builds it -- `config.switch_to_decoder` is False for the KPFCNN
+    and set to True (with `config.symmetric`) on the caller's config afterwards, so PredatorPairTrainStep(.., config) takes
+    the symmetric branch.  The optimizer gets the same two parameter groups."""
     np.random.seed(seed)                    # the KPConv kernel points are placed with NumPy's global stream
     torch.manual_seed(seed)
+    if symmetric:
+        config.symmetric, config.switch_to_decoder = True, False
     model = KPFCNN(config).to(dev)
-    gen = GenerativeMLP_98(in_channel=config.final_feats_dim, out_points=config.point_generation_ratio, radius=None,
-                           bn_momentum=config.batch_norm_momentum).to(dev)
+    if symmetric:
+        config.switch_to_decoder = True
+        gen = KPFCNNDecoder(config).to(dev)
+    else:
+        gen = GenerativeMLP_98(in_channel=config.final_feats_dim, out_points=config.point_generation_ratio, radius=None,
+                               bn_momentum=config.batch_norm_momentum).to(dev)
     opt = torch.optim.SGD([{"params": model.parameters()}, {"params": gen.parameters()}], lr=LR, momentum=MOMENTUM,
                           weight_decay=WEIGHT_DECAY)
     return model, gen, opt, torch.optim.lr_scheduler.ExponentialLR(opt, gamma=GAMMA)

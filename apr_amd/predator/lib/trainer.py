@@ -6,7 +6,8 @@ regulariser, `generated + pcd.repeat(1, ratio)` reshaped to points, Chamfer dist
 cloud, `(chamfer + regulariser * strength) * loss_ratio`.  Differentiable end to end (apr_amd/npr.py); the circle /
 overlap / saliency losses of the descriptor branch are in lib/loss.py (`MetricLoss`, on HIP kernels as well).
 
-`PredatorPairTrainStep` is the train branch of `inference_one_batch` (:147-221) for the non-symmetric model plus the
+`PredatorPairTrainStep` is the train branch of `inference_one_batch` (:147-221), for the MLP generator and -- with
+`config.symmetric` -- for the symmetric one (a KPFCNNDecoder on the encoder's descriptors, :160-164), plus the
 optimizer step and `zero_grad` of `inference_one_epoch` (:316-322): KPFCNN forward in train(), the NPR loss of both
 frames, MetricLoss, `circle * w_circle + overlap * w_overlap + saliency * w_saliency + generative_loss`, backward unless a
 Chamfer value is NaN.  The epoch loop, loader, logging and checkpoints around it stay the reference's own host code.
@@ -29,6 +30,12 @@ def npr_frame_loss(generative_model, feats, pcd, nghb, point_generation_ratio, r
     generated = generative_model(feats)
     if isinstance(generated, tuple):          # a model built with a radius returns (x, radius): models/mlp.py:140-143
         generated = generated[0]
+    return npr_generated_loss(generated, pcd, nghb, point_generation_ratio, regularization_strength, loss_ratio)
+
+
+def npr_generated_loss(generated, pcd, nghb, point_generation_ratio, regularization_strength, loss_ratio):
+    """`npr_frame_loss` from ready `generated` rows [n, ratio * 3] (lib/trainer.py:176-183): the symmetric generator makes
+    both frames' rows in one call."""
     regularize_loss = torch.mean(torch.sum((generated.reshape(-1, 3)) ** 2, axis=-1))
     mod_generated = (generated + pcd.to(generated.device).repeat(1, point_generation_ratio)).reshape(-1, 3)
     chamfer_loss_raw = chamfer_distance(mod_generated, nghb)
@@ -67,6 +74,8 @@ class PredatorPairTrainStep:
         self.point_generation_ratio = config.point_generation_ratio
         self.regularization_strength, self.loss_ratio = config.regularization_strength, config.loss_ratio
         self.validate_gradient = validate_gradient
+        # :160-164: `generative_model` is a KPFCNNDecoder fed the whole batch dict with the encoder's descriptors in it
+        self.symmetric = bool(getattr(config, "symmetric", False))
 
     def __call__(self, inputs):
         self.model.train()
@@ -80,10 +89,18 @@ class PredatorPairTrainStep:
         src_pcd, tgt_pcd = on(inputs['src_pcd_raw']), on(inputs['tgt_pcd_raw'])
         src_feats, tgt_feats = feats[:len_src], feats[len_src:]
 
-        l0, c0, r0, _ = npr_frame_loss(self.generative_model, src_feats, src_pcd, on(inputs['src_nghb']),
-                                       self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
-        l1, c1, r1, _ = npr_frame_loss(self.generative_model, tgt_feats, tgt_pcd, on(inputs['tgt_nghb']),
-                                       self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
+        if self.symmetric:                        # :160-164: one generator call for the stacked pair, split at len_src
+            inputs['second_features'] = feats     # written into the caller's dict, as the reference does
+            generated = self.generative_model(inputs)
+            l0, c0, r0, _ = npr_generated_loss(generated[:len_src], src_pcd, on(inputs['src_nghb']),
+                                               self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
+            l1, c1, r1, _ = npr_generated_loss(generated[len_src:], tgt_pcd, on(inputs['tgt_nghb']),
+                                               self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
+        else:
+            l0, c0, r0, _ = npr_frame_loss(self.generative_model, src_feats, src_pcd, on(inputs['src_nghb']),
+                                           self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
+            l1, c1, r1, _ = npr_frame_loss(self.generative_model, tgt_feats, tgt_pcd, on(inputs['tgt_nghb']),
+                                           self.point_generation_ratio, self.regularization_strength, self.loss_ratio)
         generative_loss, chamfer_loss, regularization_loss = l0 + l1, c0 + c1, r0 + r1
 
         _, count = self.desc_loss.select(src_pcd, tgt_pcd, corr, rot, trans)

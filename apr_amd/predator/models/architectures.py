@@ -33,10 +33,24 @@ def plan_architecture(config):
     conv_radius and doubles at every pooling / strided block together with the width, a 'simple' block hands on half
     of its width, the encoder stops at the first 'upsample' block; the decoder then undoes the doubling level by level
     and a block that FOLLOWS an upsampling one takes that level's skip features as extra input channels."""
+    return _plan(config, config.in_feats_dim, config.gnn_feats_dim + (2 if config.add_cross_score else 1))
+
+
+def plan_decoder_architecture(config):
+    """`plan_architecture` for KPFCNNDecoder (Predator_APR/models/architectures.py:215-317): the same walk, starting from
+    the encoder's descriptor width (final_feats_dim) instead of in_feats_dim, and with nothing between the two halves --
+    the decoder half does not jump to the conditioned width, the encoder's last output width simply halves at every
+    upsampling.  -> the same six values; the last one (the width a bottleneck would read) is unused by the generator."""
+    return _plan(config, config.final_feats_dim, None)
+
+
+def _plan(config, width_in, decoder_width):
+    """The walk behind both schedules.  `decoder_width`: the width the decoder half starts to emit (KPFCNN: the
+    conditioned bottleneck's), or None to carry the encoder's on (KPFCNNDecoder)."""
     names = list(config.architecture)
     first_up = next((i for i, n in enumerate(names) if 'upsample' in n), len(names))
     radius = config.first_subsampling_dl * config.conv_radius
-    width_in, width_out, level = config.in_feats_dim, config.first_feats_dim, 0
+    width_out, level = config.first_feats_dim, 0
     enc, skips, skip_widths = [], [], []
     for i, name in enumerate(names[:first_up + 1]):
         if 'equivariant' in name and width_out % 3 != 0:
@@ -52,8 +66,10 @@ def plan_architecture(config):
             level, radius, width_out = level + 1, radius * 2, width_out * 2
     bottleneck = width_in
     # decoder: its first block is the parameter-free upsampling one, so the width handed to it (the encoder's last,
-    # as in the reference) does not matter; from there on every block emits the conditioned width
-    width_out = config.gnn_feats_dim + (2 if config.add_cross_score else 1)
+    # as in the reference) does not matter; from there on every block of KPFCNN emits the conditioned width, while
+    # KPFCNNDecoder carries the encoder's last width on
+    if decoder_width is not None:
+        width_out = decoder_width
     dec, concats = [], []
     tail = names[first_up:]
     for j, name in enumerate(tail):
@@ -290,3 +306,55 @@ class KPFCNN(nn.Module):
         scores_overlap = kp_ops.score_head(x[:, self.final_feats_dim])
         scores_saliency = kp_ops.score_head(x[:, self.final_feats_dim + 1])
         return feats_f, scores_overlap, scores_saliency
+
+
+class KPFCNNDecoder(nn.Module):
+    """The symmetric generator of Predator_APR (models/architectures.py:215-340; `main.py:58-63` builds it in place of the
+    MLP when `symmetric` is set): a second copy of the backbone without bottleneck, GCN and projection heads, reading the
+    encoder's descriptors `batch['second_features']` [N0, final_feats_dim] and returning [N0, point_generation_ratio * 3]
+    offsets.  Attribute names, registration order and `state_dict` keys are the reference's (`epsilon` is registered first
+    and never used: it exists for the key order and a strict `load_state_dict`); built after a KPFCNN under the same NumPy
+    and torch seeds it holds the reference's parameters bit for bit.  The config must carry `switch_to_decoder = True` and
+    `symmetric = True` when it is built (`block_decider('last_unary')` takes its width from them).
+
+    Two quirks of the reference, both kept:
+      * the input is `.clone().detach()`: the generative loss trains the generator only, the encoder gets nothing from it;
+      * the output is `F.normalize(x, p=2, dim=1)` over all point_generation_ratio * 3 columns: every generated row has
+        unit length, so the trainer's "regulariser" mean(sum(offset^2)) is the constant 1 / point_generation_ratio per
+        frame (0.25), with a zero gradient up to rounding, and the generated points lie within 1 m of their anchor.
+
+    `train()` with grad enabled and parameters requiring grad: the blocks' HIP training path (the first KPConv has
+    cin = 32 and an input without gradient: apr_kpconv_weighted_c32 forward and for d W).  `eval()` or no_grad: the
+    inference kernels."""
+
+    def __init__(self, config):
+        super().__init__()
+        enc, dec, skips, skip_widths, concats, _ = plan_decoder_architecture(config)
+        self.K = config.num_kernel_points
+        self.epsilon = torch.nn.Parameter(torch.tensor(-5.0))
+        self.condition = config.condition_feature
+        self.add_cross_overlap = config.add_cross_score
+        self.encoder_blocks = nn.ModuleList(block_decider(*row, config) for row in enc)
+        self.encoder_skip_dims, self.encoder_skips = skip_widths, skips
+        self.decoder_blocks = nn.ModuleList(block_decider(*row, config) for row in dec)
+        self.decoder_concats = concats
+
+    def forward(self, batch):
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward(batch, True)
+        with torch.no_grad():
+            return self._forward(batch, False)
+
+    def _forward(self, batch, grad):
+        x = batch['second_features'].clone().detach()
+        skip_x = []
+        for block_i, block_op in enumerate(self.encoder_blocks):
+            if block_i in self.encoder_skips:
+                skip_x.append(x)
+            x = block_op(x, batch)
+        for block_i, block_op in enumerate(self.decoder_blocks):
+            if block_i in self.decoder_concats:
+                x = torch.cat([x, skip_x.pop()], dim=1)
+            x = block_op(x, batch)
+        x = x.contiguous()
+        return torch.nn.functional.normalize(x, p=2, dim=1) if grad else ops.l2_normalize(x)

@@ -999,6 +999,15 @@ int apr_row_sums(const float* x, int64_t ld, int64_t n, int32_t c, float* out, v
 int apr_kpconv_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
                         int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
                         int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream);
+/* KPConv step 1 (blocks.py:269-372) for cin = 32 on the fp32 MFMA: what apr_kpconv_weighted computes, for the first layer of
+ * the symmetric generator (KPFCNNDecoder reads the encoder's 32-d descriptors on the finest level), where
+ * apr_kpconv_weighted runs its one-thread-per-(query, kernel point) kernel.  Linear influence, sum aggregation.  Takes
+ * n_kp = 15, cin = 32, 1 <= H <= 128, ldx and ldwf even, x and wf 8-byte aligned; everything else is refused before any
+ * launch (no other route inside) and a refused call writes nothing.  nq == 0 launches nothing; columns of wf behind 480
+ * are never written; a shadow neighbour (nbr < 0 or >= ns) contributes nothing and is not counted. */
+int apr_kpconv_weighted_c32(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                            int32_t H, const float* x, int64_t ldx, int32_t cin, const float* kernel_points,
+                            int32_t n_kp, float extent, const float* rowsum, float* wf, int64_t ldwf, void* stream);
 /* Both steps of the rigid KPConv in ONE kernel (kpconv_fused.hip): out[q, :] = wf[q, :] @ W.reshape(15 cin, cout) with wf as
  * apr_kpconv_weighted defines it; the [queries, 15 cin] tile lives in LDS and registers only.  Correlation in fp32 on the
  * fp32 MFMA, contraction on the bf16 MFMA in the 3-way split (six cross terms, fp32 accumulate), no atomics: the same bits
