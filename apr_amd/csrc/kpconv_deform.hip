@@ -24,19 +24,15 @@
 // aligned rows; every sum in a fixed order (no atomics): the same bits on every run.
 //
 // Influence and aggregation (blocks.py:320-345) are compile-time parameters INF / CLOSEST of all three kernels; <kLinear,
-// false> is the code above.  For the constant and the gaussian influence the reference's re-gather DOES matter: a real
+// false> gives the formulas above.  For the constant and the gaussian influence the reference's re-gather DOES matter: a real
 // neighbour outside every deformed ball contributes nothing (in_range masks w), one inside a ball carries its influence to
 // all 15 kernel points, or with CLOSEST to its nearest one alone (kpmode::closest_kp, the same statement in every kernel).
 //   gaussian: w = exp(-d2 / (2 sigma^2 + 1e-9)), sigma = 0.3 extent;  d_dkp = mod / num * sum_{h in range} w 2 diff / (2 sigma^2 + 1e-9) P
 //   constant: w = 1;  d_dkp = 0
-#include "common.h"
-#include "kpconv_modes.h"
+#include "kpconv.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kKP = 15;
-constexpr int kMaxH = 128;
 constexpr float kShadow = 1e6f;
 
 // Step 1.  The MFMA form of k_kpconv_weighted_mfma (kpconv.hip): A = w[k = r16][h = qd] on the fly from the lane's own
@@ -57,12 +53,7 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
   __shared__ unsigned char s_cl[MODE ? 4 : 1][MODE ? kMaxH : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, qd = lane >> 4;
-  int blk = blockIdx.x;
-  if (xcd_swz) {      // consecutive queries (they share neighbours) behind ONE XCD's L2
-    const int nb = gridDim.x, xcd = blk & 7, loc = blk >> 3;
-    blk = xcd * (nb >> 3) + min(xcd, nb & 7) + loc;
-  }
-  const int qi = blk * 4 + wave;
+  const int qi = kp_xcd_block(xcd_swz) * 4 + wave;
   if (qi >= nq) return;
   const float qx = q_pts[3 * (int64_t)qi], qy = q_pts[3 * (int64_t)qi + 1], qz = q_pts[3 * (int64_t)qi + 2];
   for (int h = lane; h < kMaxH; h += 64) {
@@ -123,12 +114,10 @@ __global__ __launch_bounds__(256) void k_kpconv_deform_weighted(
       const int idx = raw & ~(1 << 30);
       float w = 0.f;
       if (kvalid && raw >= 0) {
+        // constant, gaussian: only the neighbours inside some deformed ball take part (blocks.py:298-316)
         const float ex = s_diff[wave][h][0] - kx, ey = s_diff[wave][h][1] - ky, ez = s_diff[wave][h][2] - kz;
-        if constexpr (INF == kpmode::kLinear) {
-          w = fmaxf(1.f - sqrtf(ex * ex + ey * ey + ez * ez) * inv_extent, 0.f);
-        } else {      // only the neighbours inside some deformed ball take part (blocks.py:298-316)
-          w = (s_cl[wave][h] & kpmode::kInRange) ? kpmode::influence<INF>(ex * ex + ey * ey + ez * ez, inv_extent, gden) : 0.f;
-        }
+        const bool part = INF == kpmode::kLinear || (s_cl[wave][h] & kpmode::kInRange);
+        w = part ? kpmode::influence<INF>(ex * ex + ey * ey + ez * ez, inv_extent, gden) : 0.f;
         if constexpr (CLOSEST) w = (s_cl[wave][h] & 15) == r16 ? w : 0.f;
       }
 #pragma unroll
@@ -167,7 +156,9 @@ __device__ inline int deform_index_stage(const float* __restrict__ q_pts, const 
                                          const float* __restrict__ rowsum, int qi, int ns, int lane, int* s_idx,
                                          float (*s_diff)[3], float (*s_w)[16], unsigned char* s_cl = nullptr) {
   const float qx = q_pts[3 * (int64_t)qi], qy = q_pts[3 * (int64_t)qi + 1], qz = q_pts[3 * (int64_t)qi + 2];
-  const float inv_extent = 1.f / extent, ext2 = extent * extent;
+  constexpr bool MODE = CLOSEST || INF != kpmode::kLinear;
+  [[maybe_unused]] const float inv_extent = 1.f / extent;
+  const float ext2 = extent * extent;
   [[maybe_unused]] const float gden = INF == kpmode::kGaussian ? kpmode::gauss_den(extent) : 0.f;
   int cnt = 0;
   for (int h = lane; h < kMaxH; h += 64) {
@@ -181,31 +172,22 @@ __device__ inline int deform_index_stage(const float* __restrict__ q_pts, const 
       dx = s_pts[3 * (int64_t)idx] - qx;
       dy = s_pts[3 * (int64_t)idx + 1] - qy;
       dz = s_pts[3 * (int64_t)idx + 2] - qz;
-      bool inr = false;
-      if constexpr (INF == kpmode::kLinear && !CLOSEST) {
+      // in range: a mode takes the flag from the closest kernel point's statement, <kLinear, false> from the influences' d2
+      const int cl = MODE ? kpmode::closest_kp(dx, dy, dz, kq, ext2) : 0;
+      bool inr = (cl & kpmode::kInRange) != 0;
+      if constexpr (KEEP_W || !MODE) {
 #pragma unroll
         for (int k = 0; k < kKP; ++k) {
           const float ex = dx - kq[3 * k], ey = dy - kq[3 * k + 1], ez = dz - kq[3 * k + 2];
           const float d2 = ex * ex + ey * ey + ez * ez;
-          inr = inr || d2 < ext2;
-          if (KEEP_W) s_w[h][k] = fmaxf(1.f - sqrtf(d2) * inv_extent, 0.f);
-        }
-      } else {
-        const int cl = kpmode::closest_kp(dx, dy, dz, kq, ext2);
-        inr = (cl & kpmode::kInRange) != 0;
-        if constexpr (KEEP_W) {
-#pragma unroll
-          for (int k = 0; k < kKP; ++k) {
-            const float ex = dx - kq[3 * k], ey = dy - kq[3 * k + 1], ez = dz - kq[3 * k + 2];
-            const float d2 = ex * ex + ey * ey + ez * ez;
-            float w = INF == kpmode::kLinear ? fmaxf(1.f - sqrtf(d2) * inv_extent, 0.f)
-                                             : (inr ? kpmode::influence<INF>(d2, inv_extent, gden) : 0.f);
+          if constexpr (!MODE) inr = inr || d2 < ext2;
+          if constexpr (KEEP_W) {
+            const float w = (INF == kpmode::kLinear || inr) ? kpmode::influence<INF>(d2, inv_extent, gden) : 0.f;
             s_w[h][k] = (!CLOSEST || k == (cl & 15)) ? w : 0.f;
           }
-        } else {
-          s_cl[h] = (unsigned char)cl;
         }
       }
+      if constexpr (!KEEP_W && MODE) s_cl[h] = (unsigned char)cl;
       cnt += (inr && rowsum[idx] > 0.f) ? 1 : 0;
     }
     s_idx[h] = idx;
@@ -383,12 +365,7 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
                 fn ": needs cin %% 64 == 0, cin <= 512, 1 <= H <= %d, ns > 0, extent > 0", kMaxH);                     \
   APR_CHECK_ARG(q_pts && s_pts && nbr && dkp && rowsum, fn ": null argument")
 
-static int deform_xcd() {
-  static const int s_xcd = env_int("APR_KPCONV_XCD", 1);      // A/B switch (shared with apr_kpconv_weighted)
-  return s_xcd;
-}
-
-// One body per entry point for the old signature (<kLinear, false>: the launches it always made) and its _mode form.
+// One body per operation; the entry points without a mode are the _mode ones at (linear, sum).
 template <int INF, bool CLOSEST>
 static int deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
                            const float* x, int64_t ldx, int32_t cin, const float* dkp, const float* mod, int32_t n_kp,
@@ -400,7 +377,7 @@ static int deform_weighted(const float* q_pts, int64_t nq, const float* s_pts, i
                 "apr_kpconv_deform_weighted: x / wf rows must be 16-byte aligned and at least cin / 15 cin wide");
   if (nq == 0) return APR_OK;
   const unsigned grid = (unsigned)cdiv64(nq, 4);
-  const int s_xcd = deform_xcd();
+  const int s_xcd = kpconv_xcd();
 #define APR_DW(N)                                                                                                       \
   hipLaunchKernelGGL((k_kpconv_deform_weighted<N, INF, CLOSEST>), dim3(grid), dim3(256), 0, st, q_pts, s_pts, nbr, H, x, ldx, \
                      cin, dkp, mod, extent, rowsum, wf, ldwf, min_d2, (int)nq, (int)ns, s_xcd)
@@ -416,8 +393,8 @@ APR_API int apr_kpconv_deform_weighted(const float* q_pts, int64_t nq, const flo
                                        int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dkp,
                                        const float* mod, int32_t n_kp, float extent, const float* rowsum, float* wf,
                                        int64_t ldwf, float* min_d2, void* stream) {
-  return deform_weighted<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dkp, mod, n_kp, extent, rowsum, wf,
-                                                 ldwf, min_d2, stream);
+  return apr_kpconv_deform_weighted_mode(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dkp, mod, n_kp, extent, rowsum, wf, ldwf,
+                                         min_d2, kpmode::kLinear, 0, stream);
 }
 
 #define APR_DEFORM_MODE(fn)                                                                                            \
@@ -463,8 +440,8 @@ APR_API int apr_kpconv_deform_dfeat_contrib(const float* q_pts, int64_t nq, cons
                                             const int32_t* nbr, int32_t H, const float* dwf, int64_t lddwf, int32_t cin,
                                             const float* dkp, const float* mod, int32_t n_kp, float extent,
                                             const float* rowsum, float* contrib, void* stream) {
-  return deform_dfeat_contrib<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, dkp, mod, n_kp, extent,
-                                                      rowsum, contrib, stream);
+  return apr_kpconv_deform_dfeat_contrib_mode(q_pts, nq, s_pts, ns, nbr, H, dwf, lddwf, cin, dkp, mod, n_kp, extent, rowsum,
+                                              contrib, kpmode::kLinear, 0, stream);
 }
 
 // apr_kpconv_deform_dfeat_contrib with the mode of apr_kpconv_deform_weighted_mode: d x flows through the influences the
@@ -500,8 +477,8 @@ APR_API int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float*
                                     int32_t H, const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf,
                                     const float* dkp, const float* mod, int32_t n_kp, float extent, const float* rowsum,
                                     float* d_dkp, float* d_mod, void* stream) {
-  return deform_dgeom<kpmode::kLinear, false>(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dwf, lddwf, dkp, mod, n_kp, extent,
-                                              rowsum, d_dkp, d_mod, stream);
+  return apr_kpconv_deform_dgeom_mode(q_pts, nq, s_pts, ns, nbr, H, x, ldx, cin, dwf, lddwf, dkp, mod, n_kp, extent, rowsum,
+                                      d_dkp, d_mod, kpmode::kLinear, 0, stream);
 }
 
 // apr_kpconv_deform_dgeom with the mode of apr_kpconv_deform_weighted_mode (the graph of blocks.py:284-358 differentiated

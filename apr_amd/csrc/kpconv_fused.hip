@@ -23,16 +23,13 @@
 // is staged once per workgroup in dynamic LDS, sized by H.  A 32-query tile (half the weight traffic per query, 62 KB of
 // LDS) measured 1.2 - 1.7x slower at every level of the KITTI pyramid and is not kept.
 // No atomics, fixed summation order: the same bits on every run.
-#include "common.h"
+#include "kpconv.h"
 #include "bf3.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int kKP = 15;
-constexpr int kMaxH = 128;
 constexpr int kTileRow = kKP * 32 + 4;      // words per query of the LDS tile (+4: conflict-free operand reads)
 
 template <int NC>   // NC = cout / 64 column groups of 16 per wave
@@ -53,6 +50,7 @@ __global__ __launch_bounds__(256) void k_kpconv_fused(
   const int q0 = blockIdx.x * QT;
 
   // neighbour geometry of the wave's queries, once per workgroup; absent queries and padding entries: index -1
+  // (kp_neighbour_stage's slot, in this kernel's own layout: one 16-B entry per slot, Hp slots, queries past nq staged too)
   for (int i = 0; i < NQW; ++i) {
     const int ql = wave * NQW + i, qi = q0 + ql;
     const bool live = qi < nq;
@@ -125,11 +123,10 @@ __global__ __launch_bounds__(256) void k_kpconv_fused(
 #pragma unroll
           for (int i = 0; i < NQW; ++i) {
             float w = 0.f;
-            if (kvalid && gm[u][i][3] >= 0) {
-              const float ex = __int_as_float(gm[u][i][0]) - kx, ey = __int_as_float(gm[u][i][1]) - ky,
-                          ez = __int_as_float(gm[u][i][2]) - kz;
-              w = fmaxf(1.f - sqrtf(ex * ex + ey * ey + ez * ez) * inv_extent, 0.f);
-            }
+            if (kvalid && gm[u][i][3] >= 0)
+              w = kpmode::influence<kpmode::kLinear>(
+                  kp_d2(__int_as_float(gm[u][i][0]), __int_as_float(gm[u][i][1]), __int_as_float(gm[u][i][2]), kx, ky, kz),
+                  inv_extent, 0.f);
             ca[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, b[u][i][0], ca[i][0], 0, 0, 0);
             ca[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, b[u][i][1], ca[i][1], 0, 0, 0);
           }

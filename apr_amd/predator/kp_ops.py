@@ -239,8 +239,8 @@ KPCONV_C32 = os.environ.get("APR_KPCONV_C32", "1") != "0"
 
 def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MODE):
     """KPConv step 1 -> weighted features [Nq, ld] (ld = 15*cin rounded up to 32), already / neighbour count.
-    mode = (influence, closest): apr_kpconv_weighted_mode for anything but the default.  Default mode, cin = 32, rows on
-    8-byte boundaries: apr_kpconv_weighted_c32 (KPCONV_C32)."""
+    mode = (influence, closest) of apr_kpconv_weighted_mode.  Default mode, cin = 32, rows on 8-byte boundaries:
+    apr_kpconv_weighted_c32 (KPCONV_C32)."""
     nbr = _i32(nbr, "kpconv.nbr")
     x, ldx = ops._rows(x, "kpconv.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -249,18 +249,15 @@ def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MO
     wf = torch.zeros((nq, ld), dtype=torch.float32, device=x.device) if ld != kk else \
         torch.empty((nq, ld), dtype=torch.float32, device=x.device)
     rs = row_sums(x)
-    if tuple(mode) != DEFAULT_MODE:
-        check(_lib.load().apr_kpconv_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
-                                                   nbr.shape[1], ptr(x), ldx, cin, ptr(kernel_points.contiguous()),
-                                                   kernel_points.shape[0], float(extent), ptr(rs), ptr(wf), ld, int(mode[0]),
-                                                   int(mode[1]), stream()))
-        return wf
-    entry = _lib.load().apr_kpconv_weighted
-    if KPCONV_C32 and cin == 32 and kernel_points.shape[0] == 15 and 1 <= nbr.shape[1] <= 128 and ldx % 2 == 0 \
-            and x.data_ptr() % 8 == 0:
-        entry = _lib.load().apr_kpconv_weighted_c32      # the MFMA correlation of the symmetric generator's first layer
-    check(entry(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1], ptr(x), ldx, cin,
-                ptr(kernel_points.contiguous()), kernel_points.shape[0], float(extent), ptr(rs), ptr(wf), ld, stream()))
+    qp, sp, kp = q_pts.contiguous(), s_pts.contiguous(), kernel_points.contiguous()
+    args = (ptr(qp), nq, ptr(sp), ns, ptr(nbr), nbr.shape[1], ptr(x), ldx, cin, ptr(kp), kp.shape[0], float(extent), ptr(rs),
+            ptr(wf), ld)
+    if tuple(mode) == DEFAULT_MODE and KPCONV_C32 and cin == 32 and kernel_points.shape[0] == 15 \
+            and 1 <= nbr.shape[1] <= 128 and ldx % 2 == 0 and x.data_ptr() % 8 == 0:
+        # the MFMA correlation of the symmetric generator's first layer
+        check(_lib.load().apr_kpconv_weighted_c32(*args, stream()))
+    else:
+        check(_lib.load().apr_kpconv_weighted_mode(*args, int(mode[0]), int(mode[1]), stream()))
     return wf
 
 
@@ -374,14 +371,9 @@ class KPConvFunction(torch.autograd.Function):
                 qp, sp, kp = q_pts.contiguous(), s_pts.contiguous(), kernel_points.contiguous()
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    if ctx.mode != DEFAULT_MODE:
-                        check(lib.apr_kpconv_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                                ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
-                                                                ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
-                    else:
-                        check(lib.apr_kpconv_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                           ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
-                                                           ptr(rs), ptr(contrib), stream()))
+                    check(lib.apr_kpconv_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                            ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
+                                                            ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             else:
@@ -401,9 +393,9 @@ def deform_ok(x, cin, H, K=15):
 
 
 def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=True, mode=DEFAULT_MODE):
-    """Deformable KPConv step 1 (apr_kpconv_deform_weighted) -> (wf [nq, 15 * cin], min_d2 [nq, 15] or None).
+    """Deformable KPConv step 1 (apr_kpconv_deform_weighted_mode) -> (wf [nq, 15 * cin], min_d2 [nq, 15] or None).
     dkp [nq, 15, 3]: the query's own kernel points; mod [nq, 15] or None; wf is already mod / (in-range count).
-    mode = (influence, closest): apr_kpconv_deform_weighted_mode for anything but the default."""
+    mode = (influence, closest)."""
     nbr = _i32(nbr, "kpconv_deform.nbr")
     x, ldx = ops._rows(x, "kpconv_deform.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -414,15 +406,10 @@ def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=T
     wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=x.device)
     md = torch.empty((nq, 15), dtype=torch.float32, device=x.device) if want_min_d2 else None
     rs = row_sums(x)
-    if tuple(mode) != DEFAULT_MODE:
-        check(_lib.load().apr_kpconv_deform_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
-                                                          nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent),
-                                                          ptr(rs), ptr(wf), wf.stride(0), ptr(md), int(mode[0]), int(mode[1]),
-                                                          stream()))
-        return wf, md
-    check(_lib.load().apr_kpconv_deform_weighted(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
-                                                 nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent), ptr(rs),
-                                                 ptr(wf), wf.stride(0), ptr(md), stream()))
+    check(_lib.load().apr_kpconv_deform_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
+                                                      nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent),
+                                                      ptr(rs), ptr(wf), wf.stride(0), ptr(md), int(mode[0]), int(mode[1]),
+                                                      stream()))
     return wf, md
 
 
@@ -460,7 +447,6 @@ class KPConvDeformFunction(torch.autograd.Function):
         if ctx.needs_input_grad[4]:
             wf, _ = kpconv_deform_weighted(q_pts, s_pts, inds, x, dkp, mod, ctx.extent, want_min_d2=False, mode=ctx.mode)
             dw = ops.spconv_wgrad(wf, dout, None, 1, wf.shape[1], cout)[0].reshape(K, cin, cout)
-        moded = ctx.mode != DEFAULT_MODE
         need_geom = (ctx.needs_input_grad[5] and ctx.mode[0] != 0) or (mod is not None and ctx.needs_input_grad[6])
         if ctx.needs_input_grad[3] or need_geom:
             dwf = linear(dout, pack_linear(weights.detach().reshape(K * cin, cout).t().contiguous(), bf3=False))
@@ -480,29 +466,18 @@ class KPConvDeformFunction(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    if moded:
-                        check(lib.apr_kpconv_deform_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                                       ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
-                                                                       ptr(None if md is None else md[q0:q1]), 15, ctx.extent,
-                                                                       ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
-                    else:
-                        check(lib.apr_kpconv_deform_dfeat_contrib(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                                  ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
-                                                                  ptr(None if md is None else md[q0:q1]), 15, ctx.extent, ptr(rs),
-                                                                  ptr(contrib), stream()))
+                    check(lib.apr_kpconv_deform_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
+                                                                   ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
+                                                                   ptr(None if md is None else md[q0:q1]), 15, ctx.extent,
+                                                                   ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             if need_geom:
                 ddkp = torch.empty((nq, 15, 3), dtype=torch.float32, device=x.device)
                 dmod = torch.empty((nq, 15), dtype=torch.float32, device=x.device)
-                if moded:
-                    check(lib.apr_kpconv_deform_dgeom_mode(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin,
-                                                           ptr(dwf), lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp),
-                                                           ptr(dmod), ctx.mode[0], ctx.mode[1], stream()))
-                else:
-                    check(lib.apr_kpconv_deform_dgeom(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin, ptr(dwf),
-                                                      lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp), ptr(dmod),
-                                                      stream()))
+                check(lib.apr_kpconv_deform_dgeom_mode(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin,
+                                                       ptr(dwf), lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp),
+                                                       ptr(dmod), ctx.mode[0], ctx.mode[1], stream()))
                 if mod is None:
                     dmod = None
                 if ctx.mode[0] == 0:

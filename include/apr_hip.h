@@ -1077,7 +1077,7 @@ int apr_kpconv_deform_dgeom(const float* q_pts, int64_t nq, const float* s_pts, 
  *   gaussian  w = exp(-d2 / (2 sigma^2 + 1e-9)), sigma = 0.3 extent, NOT clipped at the extent (expf)     (blocks.py:331-335)
  *   closest   w[q,k,h] is kept for k = argmin_k d2[q,h,k] alone, the lowest k winning an exact tie (torch.argmin); the
  *             one-hot mask is a constant of the graph (blocks.py:339-342).  Every kernel of a layer finds that kernel point
- *             with the same float32 statement (kpconv_modes.h).
+ *             with the same float32 statement (kpconv.h).
  * Rigid layers (apr_kpconv_weighted_mode: blocks.py:320-372; apr_kpconv_dfeat_contrib_mode: the same lines differentiated
  * with respect to x): every real neighbour takes part.  Deformable layers (apr_kpconv_deform_*_mode, blocks.py:292-358): only
  * the neighbours inside some deformed ball (d2 < extent^2 for some k, blocks.py:298-316) take part -- for the constant and

@@ -2,7 +2,7 @@
 (tests/test_attention_oracle_cpu.py confirms the planted facts from the oracle's own float64 values).  numpy only; everything
 is built on the host from small integer seeds.
 
-Kernel constants the cases are built around (apr_amd/csrc/kpconv.hip):
+Kernel constants the cases are built around (apr_amd/csrc/attention.hip):
 * k_mha: 8 queries per workgroup, 256 threads over the keys, scores [8][max(m, 256)] + queries [8][dim] in 60 KB of LDS
   (m <= 1920 - dim), dim divides 256; the value pass has ngrp = 256 / dim key groups stepping 4 * ngrp keys.
 * k_mha_mfma: dim 64, 16 queries per workgroup, 4 waves over the 16-key tiles (wave = tile % 4), online softmax, merge of 4.

@@ -1,4 +1,4 @@
-"""Float64 NumPy statement of the kernels of the overlap-attention module (apr_amd/csrc/kpconv.hip from k_edge_features
+"""Float64 NumPy statement of the kernels of the overlap-attention module (apr_amd/csrc/attention.hip from k_edge_features
 on: edge features and their backward, group max, the attention and softmax-matvec kernels, the attention's training
 path, the score head), with per-element error bounds for a float32 evaluation.  numpy only, no torch.
 
