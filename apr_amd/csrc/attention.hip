@@ -682,6 +682,29 @@ APR_API int apr_mha_train_backward(const float* q, const float* k, const float* 
   return APR_OK;
 }
 
+// the training kernels above on another unit's operands (attention_cat.hip: P, then dQ / dK from its own dS)
+int apr_internal_mha_probs(const float* q, const float* k, int32_t n, int32_t m, int32_t dim, int32_t heads, float* P, hipStream_t st) {
+  hipLaunchKernelGGL(k_mha_probs, dim3((unsigned)(n * heads)), dim3(256), (size_t)(dim + 4) * 4, st, q, k, n, m, dim, heads, P);
+  APR_LAUNCH_CHECK();
+  return APR_OK;
+}
+
+int apr_internal_mha_rowmat(const float* A, const float* X, int32_t n, int32_t m, int32_t dim, int32_t heads, float scale, float* out,
+                            hipStream_t st) {
+  const int64_t nblk = cdiv64((int64_t)n * dim * heads, 256);
+  hipLaunchKernelGGL(k_mha_rowmat, dim3((unsigned)(nblk > 16384 ? 16384 : nblk)), dim3(256), 0, st, A, X, n, m, dim, heads, scale, out);
+  APR_LAUNCH_CHECK();
+  return APR_OK;
+}
+
+int apr_internal_mha_colmat(const float* A, const float* X, int32_t n, int32_t m, int32_t dim, int32_t heads, float scale, float* out,
+                            hipStream_t st) {
+  const int64_t nblk = cdiv64((int64_t)m * dim * heads, 256);
+  hipLaunchKernelGGL(k_mha_colmat, dim3((unsigned)(nblk > 16384 ? 16384 : nblk)), dim3(256), 0, st, A, X, n, m, dim, heads, scale, out);
+  APR_LAUNCH_CHECK();
+  return APR_OK;
+}
+
 APR_API int apr_mha(const float* q, const float* k, const float* v, int32_t n, int32_t m, int32_t dim, int32_t heads,
                     float* out, void* stream) {
   APR_CHECK_ARG(n > 0 && m > 0 && dim > 0 && heads > 0, "apr_mha: bad arguments");

@@ -75,6 +75,14 @@ int apr_internal_dense_gemm(const float* in, int64_t ldi, int64_t M, int32_t cin
                             const float* scale, const float* shift, const float* residual, int64_t ldr, int32_t relu,
                             float* out, int64_t ldo, hipStream_t st);
 
+// attention.hip: the training attention's kernels on the caller's operands -- P [heads, n, m] = softmax_j(<q_i, k_j> / sqrt(dim));
+// out[i, ch] = scale * sum_j A[h, i, j] X[j, ch] (rowmat) and out[j, ch] = scale * sum_i A[h, i, j] X[i, ch] (colmat), h = ch % heads
+int apr_internal_mha_probs(const float* q, const float* k, int32_t n, int32_t m, int32_t dim, int32_t heads, float* P, hipStream_t st);
+int apr_internal_mha_rowmat(const float* A, const float* X, int32_t n, int32_t m, int32_t dim, int32_t heads, float scale, float* out,
+                            hipStream_t st);
+int apr_internal_mha_colmat(const float* A, const float* X, int32_t n, int32_t m, int32_t dim, int32_t heads, float scale, float* out,
+                            hipStream_t st);
+
 // spconv_bigk.hip: the tile family's kernel for 32 < K <= 125 (apr_spconv_bigk_supported shapes); _aligned = the 16-byte
 // rows and vectors it loads and stores by
 bool apr_internal_spconv_bigk_aligned(const apr_spconv_desc& d);

@@ -667,6 +667,105 @@ def mha_headmajor(q, k, v, heads):
     return out
 
 
+# the geometric cross attention's inference route: the MFMA kernel (dim 64); scalar = the training entry points (A/B switch)
+MHA_CAT_MFMA = os.environ.get("APR_MHA_CAT", "mfma") != "scalar"
+
+
+def _cat_coords(c, rows, name):
+    if not c.is_cuda or c.dim() != 2 or c.shape[0] != rows or c.shape[1] != 3:
+        raise _lib.AprHipError(f"{name}: need a [{rows}, 3] GPU tensor of coordinates")
+    return c.detach().to(torch.float32).contiguous()
+
+
+def mha_cat_headmajor(q, k, v, c0, c1, heads, padded=False):
+    """The geometric cross attention ('cross_cat', gcn.py:131-156) with q / k / v head-major (channel h*dim + d), dim = 64:
+    y [n, (dim+7)*heads], channel e*heads + h = feat | soft | aug1 | aug2.  The rows live in a buffer padded to the GEMM's
+    granule of 32 columns with the pad zeroed; `padded` returns that whole buffer (what `linear_padded` reads)."""
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    n, c = q.shape
+    m = k.shape[0]
+    cy = (c // heads + 7) * heads
+    ld = (cy + 31) // 32 * 32
+    c0, c1 = _cat_coords(c0, n, "mha_cat.c0"), _cat_coords(c1, m, "mha_cat.c1")      # named: a converted copy lives past the launch
+    y = torch.empty((n, ld), dtype=torch.float32, device=q.device)
+    if ld > cy:
+        y[:, cy:].zero_()
+    check(_lib.load().apr_mha_cat_headmajor(ptr(q), ptr(k), ptr(v), ptr(c0), ptr(c1), n, m, c // heads, heads, ptr(y), ld, stream()))
+    return y if padded else y[:, :cy]
+
+
+def linear_padded(xp, wp_info, shift=None):
+    """`linear` on rows the caller already padded with zeros to the packed width (no pad copy)."""
+    wp, cin, cout, cin_p, cout_p, w_bf3 = wp_info
+    if xp.shape[1] != cin_p or xp.stride(0) % 4 != 0 or xp.data_ptr() % 16 != 0 or xp.stride(1) != 1:
+        return linear(xp[:, :cin], wp_info, shift=shift)
+    if cout_p == cout and w_bf3 is not None and DENSE_BF3 and (shift is None or shift.data_ptr() % 16 == 0):
+        return ops.dense_gemm_bf3(xp, w_bf3, cin_p, cout_p, shift=shift)
+    if shift is not None and cout_p != cout:
+        shift = torch.nn.functional.pad(shift.view(-1), (0, cout_p - cout))
+    return ops.spconv(xp, None, 1, cin_p, cout_p, wp, shift=shift, n_out=xp.shape[0])[:, :cout]
+
+
+class MHACatFunction(torch.autograd.Function):
+    """The geometric cross attention on interleaved channels (c = d*heads + h) with forward and backward on the HIP kernels
+    (apr_mha_cat_train_forward / _backward): the forward keeps the probabilities and y, every sum has a fixed order.  The
+    coordinates take no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, c0, c1, heads):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        n, c = q.shape
+        m = k.shape[0]
+        c0, c1 = _cat_coords(c0, n, "mha_cat.c0"), _cat_coords(c1, m, "mha_cat.c1")
+        cy = (c // heads + 7) * heads
+        P = torch.empty((heads, n, m), dtype=torch.float32, device=q.device)
+        y = torch.empty((n, cy), dtype=torch.float32, device=q.device)
+        check(_lib.load().apr_mha_cat_train_forward(ptr(q), ptr(k), ptr(v), ptr(c0), ptr(c1), n, m, c // heads, heads, ptr(P), ptr(y),
+                                                    cy, stream()))
+        ctx.save_for_backward(q, k, v, c0, c1, P, y)
+        ctx.heads = heads
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        q, k, v, c0, c1, P, y = ctx.saved_tensors
+        heads = ctx.heads
+        n, c = q.shape
+        m = k.shape[0]
+        dy = dy.contiguous()
+        dS = torch.empty_like(P)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        check(_lib.load().apr_mha_cat_train_backward(ptr(q), ptr(k), ptr(v), ptr(c0), ptr(c1), ptr(P), ptr(y), ptr(dy), y.shape[1], n, m,
+                                                     c // heads, heads, ptr(dS), ptr(dq), ptr(dk), ptr(dv), stream()))
+        return dq, dk, dv, None, None, None
+
+
+def mha_cat_torch(q, k, v, c0, c1, heads):
+    """The layer's statement in torch ops (gcn.py:142-156 on rows): the route when HIP_TRAIN_MHA is off or dim > 1024."""
+    n, c = q.shape
+    dim = c // heads
+    qh, kh, vh = (t.view(-1, dim, heads) for t in (q, k, v))                      # channel c = d*heads + h
+    prob = torch.softmax(torch.einsum('ndh,mdh->hnm', qh, kh) / dim ** .5, dim=-1)
+    feat = torch.einsum('hnm,mdh->ndh', prob, vh)
+    soft = torch.einsum('hnm,ma->nah', prob, c1.detach().to(q.dtype))
+    aug1 = soft - c0.detach().to(q.dtype)[:, :, None]
+    aug2 = torch.norm(aug1, dim=1, keepdim=True)
+    return torch.cat([feat, soft, aug1, aug2], dim=1).reshape(n, -1)
+
+
+def mha_cat_route(q, heads):
+    """'train': `mha_cat` takes the HIP training entry points; 'torch': the torch-op statement."""
+    hip = HIP_TRAIN_MHA and q.is_cuda and q.dtype == torch.float32 and q.shape[1] // heads <= 1024
+    return 'train' if hip else 'torch'
+
+
+def mha_cat(q, k, v, c0, c1, heads):
+    """The geometric cross attention on interleaved channels: the HIP training entry points, or torch ops."""
+    if mha_cat_route(q, heads) == 'train':
+        return MHACatFunction.apply(q, k, v, c0, c1, heads)
+    return mha_cat_torch(q, k, v, c0, c1, heads)
+
+
 def softmax_matvec(a, b, w, temperature):
     a, w = a.contiguous(), w.contiguous().view(-1)
     out = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)

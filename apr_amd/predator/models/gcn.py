@@ -1,8 +1,9 @@
-"""Overlap-attention module (self / cross / self) on the HIP operator library.
+"""Overlap-attention module (self / cross / cross_cat layers) on the HIP operator library.
 
 Parameter names and module structure follow /root/reference/Predator_APR/models/gcn.py
 (SelfAttention :38-77, MLP :80-92, MultiHeadedAttention :101-116, AttentionalPropagation
-:119-128, GCN :171-205).  Features travel as row-major [N, C] tensors (the reference's [1, C, N]
+:119-128, MultiHeadedAttentionCat :131-156, AttentionalPropagationCat :159-168, GCN
+:171-205).  Features travel as row-major [N, C] tensors (the reference's [1, C, N]
 transposed); nothing of size N x N is materialised: the kNN graph comes from a brute-force kNN
 kernel, edge features are built per (point, neighbour) row, attention is a fused softmax kernel.
 """
@@ -169,6 +170,57 @@ class AttentionalPropagation(nn.Module):
         return conv1x1(h, self.mlp[3], self._c[1])
 
 
+class MultiHeadedAttentionCat(nn.Module):
+    """Cross attention that also carries geometry (reference gcn.py:131-156): beside the attended features each head returns
+    the attention-weighted mean of the other cloud's coordinates, its offset from the query point and that offset's length.
+    proj[0] IS distribute (one module under two names, as the reference has it); the 7 * 4 of merge is the reference's
+    literal, which is why its forward only works with 4 heads."""
+
+    def __init__(self, num_heads: int, d_model: int):
+        super().__init__()
+        assert d_model % num_heads == 0
+        self.dim = d_model // num_heads
+        self.num_heads = num_heads
+        self.distribute = nn.Conv1d(d_model, d_model, kernel_size=1)
+        self.proj = nn.ModuleList([self.distribute, deepcopy(self.distribute), deepcopy(self.distribute)])
+        self.merge = nn.Conv1d(d_model + 7 * 4, d_model + 7 * 4, kernel_size=1)
+        self._c = [_Packed() for _ in range(4)]
+        self._hm = [_PackedHeadMajor() for _ in range(3)]
+        self.last_route = None          # 'mfma' / 'train' / 'torch': the route the last forward took
+
+    def forward(self, query, key, value, coords0, coords1):
+        if self.num_heads != 4:
+            raise ValueError(f"cross_cat attention is defined for 4 heads only (the reference's merge is {self.dim * self.num_heads}"
+                             f" + 7 * 4 channels wide), not {self.num_heads}")
+        tracked = kp_ops.tracking(query, key, value, *self.parameters())
+        if self.dim == 64 and kp_ops.MHA_CAT_MFMA and not tracked:
+            # projections written head-major, attention on the fp32 MFMA, y in the interleaved layout on padded rows
+            packed = [c.get(l, self.num_heads) for l, c in zip(self.proj, self._hm)]
+            q, k, v = [kp_ops.linear(x, wp, shift=b) for x, (wp, b) in zip((query, key, value), packed)]
+            y = kp_ops.mha_cat_headmajor(q, k, v, coords0, coords1, self.num_heads, padded=True)
+            self.last_route = 'mfma'
+            return kp_ops.linear_padded(y, self._c[3].get(self.merge), shift=self.merge.bias.detach())
+        q, k, v = [conv1x1(x, l, c) for l, x, c in zip(self.proj, (query, key, value), self._c[:3])]
+        self.last_route = kp_ops.mha_cat_route(q, self.num_heads)
+        y = kp_ops.mha_cat(q, k, v, coords0, coords1, self.num_heads)
+        return conv1x1(y, self.merge, self._c[3])
+
+
+class AttentionalPropagationCat(nn.Module):
+    def __init__(self, feature_dim: int, num_heads: int):
+        super().__init__()
+        self.attn = MultiHeadedAttentionCat(num_heads, feature_dim)
+        self.mlp = MLP([feature_dim * 2 + 7 * 4, feature_dim * 2, feature_dim])
+        nn.init.constant_(self.mlp[-1].bias, 0.0)
+        self._c = [_Packed(), _Packed()]
+
+    def forward(self, feats0, feats1, coords0, coords1):
+        message = self.attn(feats0, feats1, feats1, coords0, coords1)
+        h = conv1x1(torch.cat([feats0, message], dim=1), self.mlp[0], self._c[0])
+        h = kp_ops.instance_norm_act(h, eps=self.mlp[1].eps, relu=True)
+        return conv1x1(h, self.mlp[3], self._c[1])
+
+
 class GCN(nn.Module):
     def __init__(self, num_head: int, feature_dim: int, k: int, layer_names: list):
         super().__init__()
@@ -176,6 +228,8 @@ class GCN(nn.Module):
         for atten_type in layer_names:
             if atten_type == 'cross':
                 layers.append(AttentionalPropagation(feature_dim, num_head))
+            elif atten_type == 'cross_cat':
+                layers.append(AttentionalPropagationCat(feature_dim, num_head))
             elif atten_type == 'self':
                 layers.append(SelfAttention(feature_dim, k))
             else:
@@ -185,9 +239,11 @@ class GCN(nn.Module):
 
     def _desc(self):
         """The module as an apr_gcn_desc (packed weights, biases, eps), or None when a layer is outside the one-call form
-        (channels not a multiple of 64, heads of another width than 64, split weights switched off); rebuilt when a
-        parameter changes."""
+        (a 'cross_cat' layer, channels not a multiple of 64, heads of another width than 64, split weights switched off);
+        rebuilt when a parameter changes."""
         from ... import _lib
+        if 'cross_cat' in self.names:      # apr_gcn_forward knows 'self' and 'cross' only
+            return None
         params = getattr(self, "_desc_params", None)
         if params is None:
             params = self._desc_params = list(self.parameters())
@@ -272,6 +328,13 @@ class GCN(nn.Module):
                 else:
                     desc0 = kp_ops.ops.affine_act(layer(desc0, desc1), residual=desc0)
                     desc1 = kp_ops.ops.affine_act(layer(desc1, desc0), residual=desc1)
+            elif name == 'cross_cat':
+                if kp_ops.tracking(desc0, desc1, *layer.parameters()):
+                    desc0 = desc0 + layer(desc0, desc1, coords0, coords1)
+                    desc1 = desc1 + layer(desc1, desc0, coords1, coords0)
+                else:
+                    desc0 = kp_ops.ops.affine_act(layer(desc0, desc1, coords0, coords1), residual=desc0)
+                    desc1 = kp_ops.ops.affine_act(layer(desc1, desc0, coords1, coords0), residual=desc1)
             elif name == 'self':
                 desc0 = layer(coords0, desc0)
                 desc1 = layer(coords1, desc1)

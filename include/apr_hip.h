@@ -1168,6 +1168,25 @@ int apr_mha_train_backward(const float* q, const float* k, const float* v, const
 int apr_mha_headmajor(const float* q, const float* k, const float* v, int32_t n, int32_t m, int32_t dim,
                       int32_t heads, float* out, void* stream);
 
+/* Geometric cross attention ('cross_cat': MultiHeadedAttentionCat, Predator_APR/models/gcn.py:131-156).  With P the
+ * attention's probabilities (scale 1 / sqrt(dim)), c0 f32 [n, 3] the queries' coordinates and c1 f32 [m, 3] the keys':
+ *   y[i, e*heads + h], e in [0, dim + 7):  e < dim: sum_j P_ij v[j, e, h];  dim .. dim+2: soft = sum_j P_ij c1[j];
+ *   dim+3 .. dim+5: aug1 = soft - c0[i];  dim+6: aug2 = ||aug1||_2.
+ * y has leading dimension ldy >= (dim + 7) * heads; columns from (dim + 7) * heads on are not written.
+ * _headmajor: the inference kernel on the fp32 MFMA; q / k / v HEAD-MAJOR and 16-byte aligned as for apr_mha_headmajor,
+ *   dim = 64 only, no limit on m.
+ * _train_forward: q / k / v interleaved, dim <= 1024; keeps P f32 [heads, n, m].
+ * _train_backward: dy f32 [n, ldy] (the gradient of y, same layout) -> dq, dk, dv; y as the forward wrote it; dS f32
+ *   [heads, n, m] is scratch.  The coordinates take no gradient; the aug2 term is 0 where aug2 == 0.  Fixed summation
+ *   orders, no float atomics: the same bits every run. */
+int apr_mha_cat_headmajor(const float* q, const float* k, const float* v, const float* c0, const float* c1, int32_t n,
+                          int32_t m, int32_t dim, int32_t heads, float* y, int64_t ldy, void* stream);
+int apr_mha_cat_train_forward(const float* q, const float* k, const float* v, const float* c0, const float* c1, int32_t n,
+                              int32_t m, int32_t dim, int32_t heads, float* P, float* y, int64_t ldy, void* stream);
+int apr_mha_cat_train_backward(const float* q, const float* k, const float* v, const float* c0, const float* c1,
+                               const float* P, const float* y, const float* dy, int64_t ldy, int32_t n, int32_t m,
+                               int32_t dim, int32_t heads, float* dS, float* dq, float* dk, float* dv, void* stream);
+
 /* The overlap-attention module of one scan pair (GCN.forward, Predator_APR/models/gcn.py:171-205: 'self' = SelfAttention
  * :38-77 on each cloud, 'cross' = AttentionalPropagation :119-128 in both directions with the residual add) as ONE call.
  * The module issued 62 library calls and 6 concatenations per pair on ~1.4 k points -- the largest share of the 110 calls
