@@ -247,6 +247,11 @@ PROTOTYPES = {
                                            _p]),
     "apr_kpconv_dfeat_contrib_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i32, _i32,
                                                 _p]),
+    # the two rigid *_mode entries for 1 <= n_kp <= 32 (csrc/kpconv_nk.hip)
+    "apr_kpconv_weighted_nk": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i64, _i32, _i32,
+                                         _p]),
+    "apr_kpconv_dfeat_contrib_nk": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _i32, _i32,
+                                              _p]),
     "apr_kpconv_deform_weighted_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p, _i64,
                                                   _p, _i32, _i32, _p]),
     "apr_kpconv_deform_dfeat_contrib_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p,

@@ -108,8 +108,12 @@ APR_API int apr_kp_resnet_block(const apr_kp_resnet_desc* dp, void* stream) {
                             d.w_kpconv, d.mid, c.kp, d.mid, stream));
     KP_TRY(kp_norm(d, c, c.kp, d.n_out, d.mid, nullptr, 0, true, c.kp, d.mid, d.seg_out, stream));
   } else {
-    KP_TRY(apr_kpconv_weighted(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp, d.extent,
-                               c.rs, c.wf, kk, stream));
+    if (d.n_kp == 15)
+      KP_TRY(apr_kpconv_weighted(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp, d.extent,
+                                 c.rs, c.wf, kk, stream));
+    else      // any other kernel-point count (1..32; kpconv_nk.hip): linear influence, sum aggregation
+      KP_TRY(apr_kpconv_weighted_nk(d.q_pts, d.n_out, d.s_pts, d.n_in, d.nbr, d.H, x1, ldx1, d.mid, d.kernel_points, d.n_kp,
+                                    d.extent, c.rs, c.wf, kk, 1, 0, stream));
     // 3. ... + InstanceNorm + LeakyReLU
     KP_TRY(kp_linear_norm(d, c, c.wf, kk, d.n_out, kk, d.mid, d.w_kpconv, nullptr, 0, true, c.kp, d.mid, d.seg_out, stream));
   }

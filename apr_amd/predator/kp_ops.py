@@ -238,9 +238,10 @@ KPCONV_C32 = os.environ.get("APR_KPCONV_C32", "1") != "0"
 
 
 def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MODE):
-    """KPConv step 1 -> weighted features [Nq, ld] (ld = 15*cin rounded up to 32), already / neighbour count.
-    mode = (influence, closest) of apr_kpconv_weighted_mode.  Default mode, cin = 32, rows on 8-byte boundaries:
-    apr_kpconv_weighted_c32 (KPCONV_C32)."""
+    """KPConv step 1 -> weighted features [Nq, ld] (ld = K*cin rounded up to 32, the padding exact zeros), already /
+    neighbour count.  mode = (influence, closest) of apr_kpconv_weighted_mode.  Default mode, cin = 32, rows on 8-byte
+    boundaries: apr_kpconv_weighted_c32 (KPCONV_C32).  K = kernel_points.shape[0] other than 15: apr_kpconv_weighted_nk
+    (1 <= K <= 32; csrc/kpconv_nk.hip)."""
     nbr = _i32(nbr, "kpconv.nbr")
     x, ldx = ops._rows(x, "kpconv.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
@@ -256,6 +257,8 @@ def kpconv_weighted(q_pts, s_pts, nbr, x, kernel_points, extent, mode=DEFAULT_MO
             and 1 <= nbr.shape[1] <= 128 and ldx % 2 == 0 and x.data_ptr() % 8 == 0:
         # the MFMA correlation of the symmetric generator's first layer
         check(_lib.load().apr_kpconv_weighted_c32(*args, stream()))
+    elif kernel_points.shape[0] != 15:
+        check(_lib.load().apr_kpconv_weighted_nk(*args, int(mode[0]), int(mode[1]), stream()))
     else:
         check(_lib.load().apr_kpconv_weighted_mode(*args, int(mode[0]), int(mode[1]), stream()))
     return wf
@@ -326,7 +329,8 @@ class KPConvFunction(torch.autograd.Function):
     d x       = scatter of (dout @ W^T) through the influences (apr_kpconv_dfeat on the forward's neighbour table).
     The points, the kernel points and the neighbour table get no gradient (rigid kernel).
     mode = (influence, closest): the *_mode entry points; d x of a mode other than the default exists in the deterministic
-    form only (apr_kpconv_dfeat_contrib_mode)."""
+    form only (apr_kpconv_dfeat_contrib_mode).  A kernel-point count other than 15 (1 <= K <= 32) runs the *_nk entry points
+    (csrc/kpconv_nk.hip): the deterministic d x only, in every mode."""
 
     @staticmethod
     def forward(ctx, q_pts, s_pts, inds, x, weights, kernel_points, extent, mode=DEFAULT_MODE):
@@ -358,6 +362,7 @@ class KPConvFunction(torch.autograd.Function):
             rs = row_sums(x)
             lib = _lib.load()
             nq, H, ns = q_pts.shape[0], inds.shape[1], s_pts.shape[0]
+            contrib_fn = lib.apr_kpconv_dfeat_contrib_mode if K == 15 else lib.apr_kpconv_dfeat_contrib_nk
             if DET_DX and cin % 4 == 0 and nq * H < (1 << 31):
                 # deterministic: one contribution row per (query, neighbour), summed per support row in the fixed order of the
                 # reverse table (no float atomics: the same bits every run).  The queries go through in chunks whose
@@ -371,14 +376,14 @@ class KPConvFunction(torch.autograd.Function):
                 qp, sp, kp = q_pts.contiguous(), s_pts.contiguous(), kernel_points.contiguous()
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    check(lib.apr_kpconv_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                            ptr(dwf[q0:q1]), lddwf, cin, ptr(kp), kp.shape[0], ctx.extent,
-                                                            ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
+                    check(contrib_fn(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H, ptr(dwf[q0:q1]), lddwf, cin,
+                                     ptr(kp), kp.shape[0], ctx.extent, ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             else:
-                if ctx.mode != DEFAULT_MODE:
-                    raise _lib.AprHipError("kpconv: the atomic d x (apr_kpconv_dfeat) is linear influence / sum aggregation only")
+                if ctx.mode != DEFAULT_MODE or K != 15:
+                    raise _lib.AprHipError("kpconv: the atomic d x (apr_kpconv_dfeat) is linear influence / sum aggregation and "
+                                           "15 kernel points only")
                 dx = torch.zeros_like(x)
                 check(lib.apr_kpconv_dfeat(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(inds), H, ptr(dwf),
                                            lddwf, cin, ptr(kernel_points.contiguous()), kernel_points.shape[0], ctx.extent,

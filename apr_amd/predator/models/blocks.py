@@ -31,6 +31,9 @@ KPCONV_DEFORM_HIP = os.environ.get("APR_KPCONV_DEFORM_HIP", "1") != "0"   # A/B 
 # 1 = KPConv builds with the constant / gaussian influence and the closest aggregation; 0 (default): the
 # constructor refuses them with NotImplementedError as before
 KPCONV_MODES = os.environ.get("APR_KPCONV_MODES", "0") != "0"
+# A/B switch: 0 = a rigid KPConv with a kernel-point count other than 15 runs the torch formulation (_forward_autograd, general
+# in K) instead of apr_kpconv_weighted_nk / apr_kpconv_dfeat_contrib_nk (1 <= K <= 32)
+KPCONV_NK_HIP = os.environ.get("APR_KPCONV_NK", "1") != "0"
 # the fused KPConv forward (apr_kpconv_fused): 0 = never, 1 = where apr_kpconv_fused_route says so, 2 = wherever it can run
 FUSED_KPCONV = int(os.environ.get("APR_KPCONV_FUSED", "0") or 0)
 KPCONV_ROUTE_HOOK = None     # set to a callable(KPConv module, nq, cin, cout, H) to observe every fused-route decision
@@ -121,6 +124,11 @@ class KPConv(nn.Module):
             self._key = key
         return self._packed
 
+    def _nk_hip(self):
+        """Do the HIP kernels take this layer's kernel-point count?  15: always (kpconv.hip); any other count: the *_nk
+        entries, 1 <= K <= 32, behind KPCONV_NK_HIP."""
+        return self.K == 15 or (KPCONV_NK_HIP and 1 <= self.K <= 32)
+
     def _fused_route(self, nq, H, aligned):
         """Does the fused kernel take this layer?  FUSED_KPCONV, the kernel's shapes, `aligned` (float32 GPU rows of
         in_channels features on 16-byte boundaries) and, at FUSED_KPCONV = 1, the measured route table."""
@@ -145,15 +153,18 @@ class KPConv(nn.Module):
             # take no gradient: its forward (the generic correlation kernel) and d W (apr_spconv_wgrad over the recomputed
             # [N, 15] weighted features) run on HIP as well
             if (self.in_channels % 64 == 0 or not x.requires_grad) and neighb_inds.shape[1] <= 128 \
-                    and self.out_channels % 32 == 0 and KPCONV_TRAIN_HIP:
-                if self._mode == kp_ops.DEFAULT_MODE:
+                    and self.out_channels % 32 == 0 and KPCONV_TRAIN_HIP and self._nk_hip():
+                if self._mode == kp_ops.DEFAULT_MODE and self.K == 15:
                     return kp_ops.KPConvFunction.apply(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points,
                                                        self.KP_extent)
-                # the other modes have the deterministic d x only (apr_kpconv_dfeat_contrib_mode)
+                # the other modes, and every kernel-point count but 15, have the deterministic d x only
+                # (apr_kpconv_dfeat_contrib_mode, apr_kpconv_dfeat_contrib_nk)
                 if not x.requires_grad or (kp_ops.DET_DX and q_pts.shape[0] * neighb_inds.shape[1] < (1 << 31)):
                     return kp_ops.KPConvFunction.apply(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points,
                                                        self.KP_extent, self._mode)
             return self._forward_autograd(q_pts, s_pts, neighb_inds, x)       # other shapes: torch ops
+        if not self._nk_hip():
+            return self._forward_autograd(q_pts, s_pts, neighb_inds, x)       # K != 15 with KPCONV_NK_HIP off, or K > 32
         prof = kp_ops.PROFILE
         if prof is not None:      # bench.py roofline leg: HIP events on the launch stream around the layer's kernels
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -382,7 +393,7 @@ class ResnetBottleneckBlock(nn.Module):
     def _fused_ok(self, features, inds):
         """One library call for the whole block (apr_kp_resnet_block): inference, InstanceNorm blocks, widths that the
         bf16-split dense GEMM takes, rows 16-byte aligned.  APR_KP_FUSED_BLOCK=0 keeps the module-by-module path."""
-        return (FUSED_BLOCK and not self.KPConv.deformable and self.KPConv._mode == kp_ops.DEFAULT_MODE and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
+        return (FUSED_BLOCK and not self.KPConv.deformable and self.KPConv._nk_hip() and self.KPConv._mode == kp_ops.DEFAULT_MODE and self.use_bn and not kp_ops.tracking(features, self.KPConv.weights) and kp_ops.PROFILE is None
                 and kp_ops.DENSE_BF3 and self.in_dim % 64 == 0 and self.out_dim % 256 == 0 and features.is_cuda
                 and features.dtype == torch.float32 and features.dim() == 2 and features.stride(1) == 1
                 and features.stride(0) % 4 == 0 and features.data_ptr() % 16 == 0 and inds.dtype == torch.int32

@@ -975,8 +975,9 @@ typedef struct apr_kp_resnet_desc {
   const int64_t* seg_in; const int64_t* seg_out;
   float* out; int64_t ldo;
   void* scratch; size_t scratch_bytes;
-  int32_t kpconv_route;      /* 0: apr_kpconv_weighted + the dense GEMM; 1: apr_kpconv_fused + InstanceNorm (the wf region of the
-                              * scratch stays unused; a shape apr_kpconv_fused_ok rejects is an argument error) */
+  int32_t kpconv_route;      /* 0: apr_kpconv_weighted (n_kp = 15; any other n_kp in 1..32: apr_kpconv_weighted_nk, linear / sum)
+                              * + the dense GEMM; 1: apr_kpconv_fused + InstanceNorm (the wf region of the scratch stays
+                              * unused; n_kp != 15 or a shape apr_kpconv_fused_ok rejects is an argument error) */
 } apr_kp_resnet_desc;
 size_t apr_kp_resnet_scratch_bytes(const apr_kp_resnet_desc* desc);
 int apr_kp_resnet_block(const apr_kp_resnet_desc* desc, void* stream);
@@ -1106,6 +1107,25 @@ int apr_kpconv_deform_dgeom_mode(const float* q_pts, int64_t nq, const float* s_
                                  const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
                                  const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
                                  int32_t influence, int32_t closest, void* stream);
+/* Rigid KPConv with any kernel-point count (the reference's num_kernel_points; csrc/kpconv_nk.hip): apr_kpconv_weighted_mode
+ * and apr_kpconv_dfeat_contrib_mode -- their arguments, contract, influences and aggregations -- for 1 <= n_kp <= 32 with
+ * kernel_points f32 [n_kp, 3], wf f32 [nq, ldwf >= n_kp * cin] (wf[q, k * cin + c], k < n_kp; nothing beyond column
+ * n_kp * cin is written) and dwf f32 [nq, lddwf >= n_kp * cin].  The two entries above stay built for 15 kernel points and
+ * refuse every other count; at n_kp = 15 these give their bits (neighbours accumulate in slot order, kernel points in
+ * ascending order, the closest kernel point is the same float32 statement with five index bits).
+ * apr_kpconv_weighted_nk: cin % 64 == 0, H <= 128 and 16-byte rows of x and wf run one wave per query on the fp32 MFMA -- one
+ * 16-row tile of kernel points for n_kp <= 16, two for 17..32 --, any other cin, H or alignment one thread per (query, kernel
+ * point).  apr_kpconv_dfeat_contrib_nk: H <= 128, cin <= 512; rows (q, h) of contrib f32 [nq * H, cin], the rows of padding
+ * neighbours untouched; apr_reverse_gather sums them.  There is no atomic form.
+ * APR_EINVAL, with a message that names the entry, before anything is read or launched: n_kp outside 1..32, an influence
+ * outside 0..2 or closest outside 0..1, H, cin or a leading dimension out of range, a null contrib.  nq = 0 returns APR_OK. */
+int apr_kpconv_weighted_nk(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                           const float* x, int64_t ldx, int32_t cin, const float* kernel_points, int32_t n_kp, float extent,
+                           const float* rowsum, float* wf, int64_t ldwf, int32_t influence, int32_t closest, void* stream);
+int apr_kpconv_dfeat_contrib_nk(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
+                                float extent, const float* rowsum, float* contrib, int32_t influence, int32_t closest,
+                                void* stream);
 size_t apr_reverse_table_scratch_bytes(int64_t nq, int32_t H, int64_t ns);
 int apr_reverse_table_build(const int32_t* nbr, int64_t nq, int32_t H, int64_t ns, int32_t* rev_t, int32_t* start,
                             void* scratch, size_t scratch_bytes, void* stream);
