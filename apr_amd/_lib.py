@@ -258,6 +258,13 @@ PROTOTYPES = {
                                                        _i32, _i32, _p]),
     "apr_kpconv_deform_dgeom_mode": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i32, _f32, _p, _p,
                                                _p, _i32, _i32, _p]),
+    # the three deformable *_mode entries for 1 <= n_kp <= 32 (csrc/kpconv_deform_nk.hip)
+    "apr_kpconv_deform_weighted_nk": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p, _i64,
+                                                _p, _i32, _i32, _p]),
+    "apr_kpconv_deform_dfeat_contrib_nk": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p,
+                                                     _i32, _i32, _p]),
+    "apr_kpconv_deform_dgeom_nk": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i32, _f32, _p, _p,
+                                             _p, _i32, _i32, _p]),
     "apr_reverse_table_scratch_bytes": (_sz, [_i64, _i32, _i64]),
     "apr_reverse_table_build": (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p, _sz, _p]),
     "apr_reverse_gather": (C.c_int, [_p, _i32, _p, _p, _i64, _p, _i64, _p]),

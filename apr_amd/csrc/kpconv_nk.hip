@@ -8,26 +8,9 @@
 // rows k >= n_kp carry w = 0 and are not stored; the feature gradient sizes its LDS influence table and its per-lane dwf
 // registers by the tile count.  Neighbours accumulate in slot order, kernel points in ascending order, with the influence
 // statements of kpconv.h: at n_kp = 15 the bits of apr_kpconv_weighted_mode / apr_kpconv_dfeat_contrib_mode (dfeat_d2 below).
-#include "kpconv.h"
+#include "kpconv_nk.h"      // kMaxKP, closest_kp_nk (shared with kpconv_deform_nk.hip)
 
 namespace {
-
-constexpr int kMaxKP = 32;
-
-// kpmode::closest_kp for n_kp kernel points: the same float32 statement (d2 in a fixed evaluation order, strict <, the
-// lowest index wins an exact tie), the index in bits 0..4, the in-range flag in bit 7.  Forward and backward both call it.
-__device__ inline int closest_kp_nk(float dx, float dy, float dz, const float* __restrict__ kpts, int n_kp, float ext2) {
-  int best = 0;
-  float bd = __builtin_inff();
-  bool inr = false;
-  for (int k = 0; k < n_kp; ++k) {
-    const float ex = dx - kpts[3 * k], ey = dy - kpts[3 * k + 1], ez = dz - kpts[3 * k + 2];
-    const float d2 = __fmaf_rn(ez, ez, __fmaf_rn(ey, ey, ex * ex));
-    if (d2 < bd) { bd = d2; best = k; }
-    inr = inr || d2 < ext2;
-  }
-  return best | (inr ? kpmode::kInRange : 0);
-}
 
 // Step 1, MFMA form.  One wave per query; cin % 64 == 0; T 16-row tiles of kernel points, NG 64-channel groups per pass
 // (T * NG * 16 accumulator registers: <1, 4> and <2, 2> hold 64, the budget of k_kpconv_weighted_mfma<4>).

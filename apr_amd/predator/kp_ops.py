@@ -392,35 +392,41 @@ class KPConvFunction(torch.autograd.Function):
 
 
 def deform_ok(x, cin, H, K=15):
-    """Shapes and layouts the deformable kernels take (apr_kpconv_deform_*): 15 kernel points, cin a multiple of 64 up to
-    512, 1 <= H <= 128, float32 GPU rows on 16-byte boundaries.  Everything else runs the torch formulation."""
-    return K == 15 and cin % 64 == 0 and 64 <= cin <= 512 and 1 <= H <= 128 and rows_aligned(x, cin)
+    """Shapes and layouts the deformable kernels take (apr_kpconv_deform_*_mode at 15 kernel points, apr_kpconv_deform_*_nk at
+    any other count from 1 to 32): cin a multiple of 64 up to 512, 1 <= H <= 128, float32 GPU rows on 16-byte boundaries.
+    Everything else runs the torch formulation.  (d W goes through apr_spconv_wgrad over [nq, K cin]: it tiles any width,
+    so K cin up to 32 * 512 = 16384 stays on the kernels.)"""
+    return 1 <= K <= 32 and cin % 64 == 0 and 64 <= cin <= 512 and 1 <= H <= 128 and rows_aligned(x, cin)
 
 
 def kpconv_deform_weighted(q_pts, s_pts, nbr, x, dkp, mod, extent, want_min_d2=True, mode=DEFAULT_MODE):
-    """Deformable KPConv step 1 (apr_kpconv_deform_weighted_mode) -> (wf [nq, 15 * cin], min_d2 [nq, 15] or None).
-    dkp [nq, 15, 3]: the query's own kernel points; mod [nq, 15] or None; wf is already mod / (in-range count).
+    """Deformable KPConv step 1 -> (wf [nq, K * cin], min_d2 [nq, K] or None), K = dkp.shape[1]: 15 kernel points run
+    apr_kpconv_deform_weighted_mode, any other count from 1 to 32 apr_kpconv_deform_weighted_nk (csrc/kpconv_deform_nk.hip).
+    dkp [nq, K, 3]: the query's own kernel points; mod [nq, K] or None; wf is already mod / (in-range count).
     mode = (influence, closest)."""
     nbr = _i32(nbr, "kpconv_deform.nbr")
     x, ldx = ops._rows(x, "kpconv_deform.x")
     nq, ns, cin = q_pts.shape[0], s_pts.shape[0], x.shape[1]
-    if tuple(dkp.shape) != (nq, 15, 3) or (mod is not None and tuple(mod.shape) != (nq, 15)):
-        raise _lib.AprHipError("kpconv_deform: dkp must be [nq, 15, 3] and mod [nq, 15]")
+    K = dkp.shape[1] if dkp.dim() == 3 else 0
+    if tuple(dkp.shape) != (nq, K, 3) or not 1 <= K <= 32 or (mod is not None and tuple(mod.shape) != (nq, K)):
+        raise _lib.AprHipError("kpconv_deform: dkp must be [nq, K, 3] with 1 <= K <= 32 and mod [nq, K]")
+    assert (K * cin) % 64 == 0      # cin % 64 == 0 (deform_ok): the packed weight rows need no zero padding
     dkp = dkp.detach().to(torch.float32).contiguous()
     mod = None if mod is None else mod.detach().to(torch.float32).contiguous()
-    wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=x.device)
-    md = torch.empty((nq, 15), dtype=torch.float32, device=x.device) if want_min_d2 else None
+    wf = torch.empty((nq, K * cin), dtype=torch.float32, device=x.device)
+    md = torch.empty((nq, K), dtype=torch.float32, device=x.device) if want_min_d2 else None
     rs = row_sums(x)
-    check(_lib.load().apr_kpconv_deform_weighted_mode(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr),
-                                                      nbr.shape[1], ptr(x), ldx, cin, ptr(dkp), ptr(mod), 15, float(extent),
-                                                      ptr(rs), ptr(wf), wf.stride(0), ptr(md), int(mode[0]), int(mode[1]),
-                                                      stream()))
+    lib = _lib.load()
+    fn = lib.apr_kpconv_deform_weighted_mode if K == 15 else lib.apr_kpconv_deform_weighted_nk
+    check(fn(ptr(q_pts.contiguous()), nq, ptr(s_pts.contiguous()), ns, ptr(nbr), nbr.shape[1], ptr(x), ldx, cin, ptr(dkp),
+             ptr(mod), K, float(extent), ptr(rs), ptr(wf), wf.stride(0), ptr(md), int(mode[0]), int(mode[1]), stream()))
     return wf, md
 
 
 class KPConvDeformFunction(torch.autograd.Function):
     """Deformable / modulated KPConv (blocks.py:229-374) on the HIP kernels, given the query's kernel points dkp
-    [nq, 15, 3] and modulations mod [nq, 15] (or None): returns (out, min_d2).
+    [nq, K, 3] and modulations mod [nq, K] (or None): returns (out, min_d2).  K = 15 runs the apr_kpconv_deform_*_mode
+    entries, any other count from 1 to 32 the apr_kpconv_deform_*_nk ones (csrc/kpconv_deform_nk.hip).
     forward   wf = apr_kpconv_deform_weighted, out = wf @ W (dense MFMA GEMM); min_d2 is not differentiable (nothing in the
               reference differentiates it);
     d W       = wf^T @ dout (apr_spconv_wgrad; wf recomputed);
@@ -462,6 +468,8 @@ class KPConvDeformFunction(torch.autograd.Function):
             qp, sp = q_pts.contiguous(), s_pts.contiguous()
             kd = dkp.detach().contiguous()
             md = None if mod is None else mod.detach().contiguous()
+            contrib_fn = lib.apr_kpconv_deform_dfeat_contrib_mode if K == 15 else lib.apr_kpconv_deform_dfeat_contrib_nk
+            dgeom_fn = lib.apr_kpconv_deform_dgeom_mode if K == 15 else lib.apr_kpconv_deform_dgeom_nk
             if ctx.needs_input_grad[3]:
                 if nq * H >= (1 << 31):
                     raise _lib.AprHipError("kpconv_deform: neighbour table too large for the reverse table")
@@ -471,18 +479,16 @@ class KPConvDeformFunction(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 for q0 in range(0, nq, qc):
                     q1 = min(nq, q0 + qc)
-                    check(lib.apr_kpconv_deform_dfeat_contrib_mode(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H,
-                                                                   ptr(dwf[q0:q1]), lddwf, cin, ptr(kd[q0:q1]),
-                                                                   ptr(None if md is None else md[q0:q1]), 15, ctx.extent,
-                                                                   ptr(rs), ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
+                    check(contrib_fn(ptr(qp[q0:q1]), q1 - q0, ptr(sp), ns, ptr(inds[q0:q1]), H, ptr(dwf[q0:q1]), lddwf, cin,
+                                     ptr(kd[q0:q1]), ptr(None if md is None else md[q0:q1]), K, ctx.extent, ptr(rs),
+                                     ptr(contrib), ctx.mode[0], ctx.mode[1], stream()))
                     check(lib.apr_reverse_gather_range(ptr(contrib), cin, ptr(rev_t), ptr(start), ns, q0 * H, q1 * H,
                                                        int(q0 > 0), ptr(dx), dx.stride(0), stream()))
             if need_geom:
-                ddkp = torch.empty((nq, 15, 3), dtype=torch.float32, device=x.device)
-                dmod = torch.empty((nq, 15), dtype=torch.float32, device=x.device)
-                check(lib.apr_kpconv_deform_dgeom_mode(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin,
-                                                       ptr(dwf), lddwf, ptr(kd), ptr(md), 15, ctx.extent, ptr(rs), ptr(ddkp),
-                                                       ptr(dmod), ctx.mode[0], ctx.mode[1], stream()))
+                ddkp = torch.empty((nq, K, 3), dtype=torch.float32, device=x.device)
+                dmod = torch.empty((nq, K), dtype=torch.float32, device=x.device)
+                check(dgeom_fn(ptr(qp), nq, ptr(sp), ns, ptr(inds), H, ptr(x), x.stride(0), cin, ptr(dwf), lddwf, ptr(kd),
+                               ptr(md), K, ctx.extent, ptr(rs), ptr(ddkp), ptr(dmod), ctx.mode[0], ctx.mode[1], stream()))
                 if mod is None:
                     dmod = None
                 if ctx.mode[0] == 0:

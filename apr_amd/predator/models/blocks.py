@@ -197,7 +197,9 @@ class KPConv(nn.Module):
     def _forward_deformable(self, q_pts, s_pts, inds, x):
         """blocks.py:235-262 (offsets and modulations from the rigid offset_conv: elementwise glue on torch ops), then the
         deformed convolution on apr_kpconv_deform_* inside the kernels' limits (kp_ops.deform_ok), in inference and in
-        training; every other shape, and APR_KPCONV_DEFORM_HIP=0, takes the torch formulation."""
+        training -- the *_mode entries at 15 kernel points, the *_nk entries (csrc/kpconv_deform_nk.hip) at
+        any other count from 1 to 32, behind KPCONV_NK_HIP as the rigid *_nk kernels are; every other shape,
+        APR_KPCONV_DEFORM_HIP=0 and, for a count other than 15, APR_KPCONV_NK=0 take the torch formulation."""
         of = self.offset_conv(q_pts, s_pts, inds, x) + self.offset_bias
         self.offset_features = of
         n3 = self.p_dim * self.K
@@ -211,7 +213,8 @@ class KPConv(nn.Module):
         tracked = kp_ops.tracking(x, self.weights, of)
         if x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and not kp_ops.rows_aligned(x, self.in_channels):
             x = x.contiguous()
-        if KPCONV_DEFORM_HIP and self.p_dim == 3 and kp_ops.deform_ok(x, self.in_channels, inds.shape[1], self.K) \
+        if KPCONV_DEFORM_HIP and (self.K == 15 or KPCONV_NK_HIP) and self.p_dim == 3 \
+                and kp_ops.deform_ok(x, self.in_channels, inds.shape[1], self.K) \
                 and q_pts.shape[0] > 0 and (not tracked or self.out_channels % 32 == 0):
             if tracked:
                 if self._mode == kp_ops.DEFAULT_MODE:

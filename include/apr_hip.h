@@ -1126,6 +1126,30 @@ int apr_kpconv_dfeat_contrib_nk(const float* q_pts, int64_t nq, const float* s_p
                                 const float* dwf, int64_t lddwf, int32_t cin, const float* kernel_points, int32_t n_kp,
                                 float extent, const float* rowsum, float* contrib, int32_t influence, int32_t closest,
                                 void* stream);
+/* Deformable / modulated KPConv with any kernel-point count (csrc/kpconv_deform_nk.hip): the three apr_kpconv_deform_*_mode
+ * entries -- their arguments, contract, influences, aggregations and deviation at d = 0 -- for 1 <= n_kp <= 32 with dkp f32
+ * [nq, n_kp, 3], mod f32 [nq, n_kp] or null, min_d2 f32 [nq, n_kp] or null, wf f32 [nq, ldwf >= n_kp * cin] (wf[q, k * cin +
+ * c], k < n_kp), dwf f32 [nq, lddwf >= n_kp * cin], d_dkp f32 [nq, n_kp, 3], d_mod f32 [nq, n_kp].  The entries above stay
+ * built for 15 kernel points and refuse every other count; at n_kp = 15 these agree with them inside the float32 error
+ * bounds of both (not bit for bit: the squared distance is contracted differently).  One wave per query on the fp32 MFMA,
+ * one 16-row tile of kernel points for n_kp <= 16, two for 17..32; the closest kernel point is closest_kp_nk's float32
+ * statement (five index bits, the lowest index wins a tie) in all three.  The same shape limits: cin % 64 == 0,
+ * 64 <= cin <= 512, 1 <= H <= 128, ns > 0, extent > 0, 16-byte aligned rows of x, wf and dwf.
+ * APR_EINVAL, with a message that names the entry, before anything is read, written or launched: n_kp outside 1..32, an
+ * influence outside 0..2 or closest outside 0..1, a shape or leading dimension out of range, a misaligned row, a null
+ * buffer.  nq = 0 returns APR_OK.  No atomics, fixed summation orders: the same bits on every run. */
+int apr_kpconv_deform_weighted_nk(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                                  const float* x, int64_t ldx, int32_t cin, const float* dkp, const float* mod, int32_t n_kp,
+                                  float extent, const float* rowsum, float* wf, int64_t ldwf, float* min_d2, int32_t influence,
+                                  int32_t closest, void* stream);
+int apr_kpconv_deform_dfeat_contrib_nk(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr,
+                                       int32_t H, const float* dwf, int64_t lddwf, int32_t cin, const float* dkp,
+                                       const float* mod, int32_t n_kp, float extent, const float* rowsum, float* contrib,
+                                       int32_t influence, int32_t closest, void* stream);
+int apr_kpconv_deform_dgeom_nk(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int32_t* nbr, int32_t H,
+                               const float* x, int64_t ldx, int32_t cin, const float* dwf, int64_t lddwf, const float* dkp,
+                               const float* mod, int32_t n_kp, float extent, const float* rowsum, float* d_dkp, float* d_mod,
+                               int32_t influence, int32_t closest, void* stream);
 size_t apr_reverse_table_scratch_bytes(int64_t nq, int32_t H, int64_t ns);
 int apr_reverse_table_build(const int32_t* nbr, int64_t nq, int32_t H, int64_t ns, int32_t* rev_t, int32_t* start,
                             void* scratch, size_t scratch_bytes, void* stream);
